@@ -14,12 +14,23 @@ single RCCL gather of every rank's draws to rank 0.  Inputs are staged in HBM
 
     value = n_gpus * chains * samples / (max over ranks of wall per step)
 
-Extra objects on the JSON line: ``roofline`` (FP64 vector roofline of the
+A plain run sets up, warms up, times the steps and prints the JSON line: the
+headline figure, ``ms_per_step`` and ``roofline`` (FP64 vector roofline of the
 sampler kernel: algorithmic flop F_grad = 4*N*Nn + 20*N per gradient, SURVEY.md
 §8d, x leapfrogs counted by the kernel / kernel time from HIP events on the
-launch stream; HBM traffic from the committed rocprofv3 PMC summary) and
-``cpu_baseline`` (the C oracle NUTS on this host's cores, bounded sample, scaled
-to the same unit -- see DESIGN.md §Measurement).
+launch stream of the timed steps themselves; HBM traffic from the committed
+rocprofv3 PMC summary).
+
+``--dump-outputs DIR`` writes what the last timed step returned to its caller (draws,
+step sizes, inverse metric, last positions) as ``DIR/<name>.npy`` (float64; a fixed,
+seeded sample of the chains when the whole exceeds 64 MB, their indices in
+``chains.npy``).  Inputs and seeds depend on the arguments alone.
+
+``--full`` adds everything that takes work of its own: the last step's convergence
+figures (R-hat, ESS, trapped chains), ``cpu_baseline`` (the C oracle NUTS on this
+host's cores, bounded sample, scaled to the same unit -- see DESIGN.md §Measurement),
+the posterior means against it, the hard-geometry sub-line, config 5's
+strong-scaling estimate and, under torchrun, the device-list sub-line.
 """
 from __future__ import annotations
 
@@ -232,6 +243,26 @@ def convergence(draws, W_saved, cols):
                                              sorted(ess.items(), key=lambda t: t[1])[:3]]}
 
 
+DUMP_BUDGET = 64 * 10**6   # bytes over all files of one --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: every array of `arrays` (each indexed by chain on its first
+    axis) as ``path/<name>.npy`` in float64.  Above DUMP_BUDGET bytes in all, the same
+    seeded subset of the chains is kept in every array; ``chains.npy`` lists it."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    C = next(iter(arrays.values())).shape[0]
+    per_chain = sum(a[0].nbytes for a in arrays.values()) + 8
+    keep = np.arange(C)
+    if C * per_chain > DUMP_BUDGET:
+        n = max(1, DUMP_BUDGET // per_chain)
+        keep = np.sort(np.random.default_rng(0).choice(C, size=n, replace=False))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a[keep]))
+    np.save(os.path.join(path, "chains.npy"), keep.astype(np.float64))
+
+
 def load_traffic(workload):
     import glob
     for path in sorted(glob.glob(TRAFFIC_GLOB), reverse=True):
@@ -256,15 +287,23 @@ def main():
     ap.add_argument("--chains", type=int, default=0, help="chains per GPU (0: the config's)")
     ap.add_argument("--iters", type=str, default=f"{WARMUP_IT},{SAMPLES}",
                     help="sampler warmup,samples per chain")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements and checks beside the headline figure: "
+                         "convergence of the last step, cpu_baseline, posterior means against "
+                         "it, the hard-geometry sub-line, config 5's strong-scaling estimate, "
+                         "the device-list sub-line under torchrun")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true",
+                    help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--precision", default="f64", choices=["f64", "mixed"])
     ap.add_argument("--adapt-delta", type=float, default=0.8,
                     help="0.8: rstan's default (the headline); 0.99 with --max-treedepth 12 is "
                          "the reference's hard-geometry profile (Tests/testGamma.R:45)")
     ap.add_argument("--max-treedepth", type=int, default=10)
     ap.add_argument("--no-hard", action="store_true",
-                    help="skip the hard-geometry sub-line (one extra config-3 step at "
-                         "adapt_delta 0.99, max_treedepth 12; N = 1 only)")
+                    help="with --full: skip the hard-geometry sub-line (one extra config-3 step "
+                         "at adapt_delta 0.99, max_treedepth 12; N = 1 only)")
     ap.add_argument("--devices", type=int, default=0,
                     help="the single-process route: one plan over the C ABI's device list "
                          "(fitoct_config.devices, what R's fitExpGP(n_gpus = N) drives through "
@@ -275,8 +314,8 @@ def main():
                     help="explicit ordinals for --devices, e.g. 0,0 rehearses two entries on "
                          "one GPU")
     ap.add_argument("--no-device-list", action="store_true",
-                    help="under torchrun (N > 1): skip the device-list sub-line that rank 0 "
-                         "times over all N GPUs after the per-rank steps")
+                    help="with --full under torchrun (N > 1): skip the device-list sub-line "
+                         "that rank 0 times over all N GPUs after the per-rank steps")
     args = ap.parse_args()
     if args.config == 5 and args.iters == f"{WARMUP_IT},{SAMPLES}":
         args.iters = "%d,%d" % CONFIGS[5]["iters"]
@@ -390,7 +429,14 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
 
-    outs = [pl.download(with_draws=(i == len(plans) - 1)) for i, pl in enumerate(plans)]
+    # the last step's draws come to the host only for --full's figures and --dump-outputs
+    want_draws = args.full or (bool(args.dump_outputs) and rank == 0)
+    outs = [pl.download(with_draws=(want_draws and i == len(plans) - 1))
+            for i, pl in enumerate(plans)]
+    if args.dump_outputs and rank == 0:
+        o = outs[-1]
+        dump_outputs(args.dump_outputs, {"draws": o.draws, "stepsize": o.stepsize,
+                                         "inv_metric": o.inv_metric, "last_q": o.last_q})
     lf_steps = [o.total_leapfrogs for o in outs]
     if dist is not None:
         t = torch.tensor(lf_steps, dtype=torch.float64, device=cdev)
@@ -408,12 +454,14 @@ def main():
     last = outs[-1].draws
     cols = prob.column_names()
     W_saved = outs[-1].warmup_saved
-    conv_draws = last
-    if world > 1 and rank == 0 and "gather" in bufs:
-        shp = last.shape
-        conv_draws = np.concatenate([g.cpu().numpy().reshape(shp) for g in bufs["gather"]])
-    conv = convergence(conv_draws, W_saved, cols)
-    conv["rhat_chains"] = int(conv_draws.shape[0])
+    conv = {}
+    if args.full:
+        conv_draws = last
+        if world > 1 and rank == 0 and "gather" in bufs:
+            shp = last.shape
+            conv_draws = np.concatenate([g.cpu().numpy().reshape(shp) for g in bufs["gather"]])
+        conv = convergence(conv_draws, W_saved, cols)
+        conv["rhat_chains"] = int(conv_draws.shape[0])
     lf_per_draw = float(np.mean(lf_steps)) / (C_plan * (W_it + S_it))
 
     workload = (f"fitExpGP+{conf['prior']} N={N_bins} Nn={NN} {C} chains/GPU "
@@ -452,14 +500,15 @@ def main():
                              "torch.distributed" if world > 1 else "single-device")},
         **conv,
         "gradients_per_iteration": round(lf_per_draw, 1),
-        # sampling phase alone (SURVEY.md §8d): the kernel is gradient-bound, so its time is
-        # apportioned by the post-warmup share of the last step's gradients (rank 0's chains)
-        "sampling_only_draws_per_s_est": round(
-            draws_step / (kms / 1e3 * float(last[:, W_saved:, 4].sum()) / outs[-1].total_leapfrogs), 1),
         "total_gradients_per_step": float(lf_all.mean()),
         "roofline": roof,
     }
-    if rank == 0 and n_units == 1 and not args.no_cpu:
+    if args.full:
+        # sampling phase alone (SURVEY.md §8d): the kernel is gradient-bound, so its time is
+        # apportioned by the post-warmup share of the last step's gradients (rank 0's chains)
+        post_share = float(last[:, W_saved:, 4].sum()) / outs[-1].total_leapfrogs
+        line["sampling_only_draws_per_s_est"] = round(draws_step / (kms / 1e3 * post_share), 1)
+    if args.full and rank == 0 and n_units == 1 and not args.no_cpu:
         cb = cpu_baseline(prob, float(np.mean(lf_steps)), C * S_it, args.adapt_delta,
                           args.max_treedepth, same_length=(W_it, S_it))
         o_means = cb.pop("means")
@@ -474,13 +523,14 @@ def main():
     for pl in plans:
         pl.close()
     bufs.clear()
-    if (args.config == 3 and n_units == 1 and not args.no_hard and args.adapt_delta == 0.8
+    if (args.full and args.config == 3 and n_units == 1 and not args.no_hard
+            and args.adapt_delta == 0.8
             and args.chains == 0 and (W_it, S_it) == (WARMUP_IT, SAMPLES)):
         line["hard_geometry"] = hard_geometry(prob, C, local, dev, W_it, S_it, cols,
                                               line.get("cpu_baseline"),
                                               o_means if "cpu_baseline" in line else None,
                                               seed=HARD_SEED)
-    if world > 1 and not args.no_device_list:
+    if args.full and world > 1 and not args.no_device_list:
         # the route R takes (.Call -> fitoct_config.devices), timed on the same node: rank 0
         # alone drives every GPU of the job from one process while the other ranks wait on
         # a host (gloo) barrier, so no collective kernel occupies their GPUs meanwhile
@@ -688,12 +738,19 @@ def bench_batch(args, world, rank, local, dev, dist, backend, cdev, W_it, S_it, 
         wall = float(t.item())
 
     last = batches[-1]
-    outs = [last.download(p) for p in range(len(probs))]
+    # the last step's draws come to the host only for --full's figures and --dump-outputs
+    want_draws = args.full or (bool(args.dump_outputs) and rank == 0)
+    outs = [last.download(p, with_draws=want_draws) for p in range(len(probs))]
+    if args.dump_outputs and rank == 0:   # file p's chains are rows p*C .. p*C + C - 1
+        dump_outputs(args.dump_outputs,
+                     {k: np.concatenate([getattr(o, k) for o in outs])
+                      for k in ("draws", "stepsize", "inv_metric", "last_q")})
     kernel_ms = float(np.mean([b.download(0, with_draws=False).kernel_ms for b in batches]))
     lf = sum(o.total_leapfrogs for o in outs)
     cols = probs[0].column_names()
     par = [j for j in range(7, len(cols))]
-    rh_file = [max(split_rhat_ess(o.draws[:, o.warmup_saved:, j])[0] for j in par) for o in outs]
+    rh_file = [max(split_rhat_ess(o.draws[:, o.warmup_saved:, j])[0] for j in par)
+               for o in outs] if args.full else []
     ms_per_step = wall * 1e3 / args.steps
     draws_step = conf["files"] * C * S_it
     achieved = f_grad(conf["N"], NN) * lf / (kernel_ms / 1e3) / 1e12
@@ -712,16 +769,17 @@ def bench_batch(args, world, rank, local, dev, dist, backend, cdev, W_it, S_it, 
                                                        "process)" if dev_list else "")),
                    "route": ("device-list" if dev_list else
                              "torch.distributed" if world > 1 else "single-device")},
-        "rhat_max_median_file": round(float(np.median(rh_file)), 4),
-        "rhat_max_worst_file": round(float(np.max(rh_file)), 4),
-        # the Shiny app paints R-hat >= 1.1 red (ShinyInterface/server.R:98-100); the C
-        # oracle on the same 256 files gives 27 / 256 (tests/golden/batch_files.npz)
-        "rhat_files_ge_1_1": round(float(np.mean(np.array(rh_file) >= 1.1)), 4),
         "roofline": {"bound": "valu", "achieved": round(achieved, 3), "peak": FP64_VALU_PEAK_TF,
                      "unit": "TFLOP/s", "frac": round(achieved / FP64_VALU_PEAK_TF, 4),
                      "traffic": None, "kernel": "nuts_kernel (batched)",
                      "kernel_ms": round(kernel_ms, 2), "gradients_per_launch_rank0": lf},
     }
+    if args.full:
+        line["rhat_max_median_file"] = round(float(np.median(rh_file)), 4)
+        line["rhat_max_worst_file"] = round(float(np.max(rh_file)), 4)
+        # the Shiny app paints R-hat >= 1.1 red (ShinyInterface/server.R:98-100); the C
+        # oracle on the same 256 files gives 27 / 256 (tests/golden/batch_files.npz)
+        line["rhat_files_ge_1_1"] = round(float(np.mean(np.array(rh_file) >= 1.1)), 4)
     traffic = load_traffic(line["config"]["workload"])
     if traffic:
         r = line["roofline"]
@@ -729,7 +787,7 @@ def bench_batch(args, world, rank, local, dev, dist, backend, cdev, W_it, S_it, 
         r["hbm_gbs"] = round(traffic["bytes_per_launch"] / (kernel_ms / 1e3) / 1e9, 2)
         r["hbm_frac"] = round(r["hbm_gbs"] / HBM_PEAK_GBS, 5)
         r["traffic_source"] = traffic["source"]
-    if rank == 0 and n_units == 1 and not args.no_cpu:
+    if args.full and rank == 0 and n_units == 1 and not args.no_cpu:
         cb = batch_cpu_baseline(file_problems, conf["files"], C, W_it, S_it, 2000 + args.steps - 1,
                                 outs)
         line["posterior_mean_relerr_vs_cpu"] = cb.pop("relerr")
@@ -738,14 +796,14 @@ def bench_batch(args, world, rank, local, dev, dist, backend, cdev, W_it, S_it, 
     for b in batches:
         b.close()
     bufs.clear()
-    if n_units == 1:
+    if args.full and n_units == 1:
         # Config 5 scales strongly (256 files in total), and each GPU's share is an
         # independent launch: N GPUs take as long as 256/N files on one GPU (plus the
         # gather), which this GPU measures -- the floor being one file's slowest chain.
         line["strong_scaling_est"] = strong_scaling_est(
             lambda n: batch_for(0, file_problems(0, conf["files"] // n), 0),
             conf["files"], C * S_it, line["ms_per_step"])
-    if world > 1 and not args.no_device_list:
+    if args.full and world > 1 and not args.no_device_list:
         hb = dist.new_group(backend="gloo")   # host barrier: no collective kernel on the GPUs
         dist.barrier(group=hb)
         if rank == 0:

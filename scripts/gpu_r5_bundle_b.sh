@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/r5bundle
 mkdir -p $OUT
 for c in 2 4 5; do
-  timeout -k 10 400 python3 bench.py --config $c --steps 2 --warmup 1 > $OUT/config$c.json 2> $OUT/config$c.err || { tail -5 $OUT/config$c.err; exit 1; }
+  timeout -k 10 400 python3 bench.py --full --config $c --steps 2 --warmup 1 > $OUT/config$c.json 2> $OUT/config$c.err || { tail -5 $OUT/config$c.err; exit 1; }
   head -c 600 $OUT/config$c.json; echo
 done
 for c in 2 4 5; do

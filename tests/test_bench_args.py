@@ -83,3 +83,34 @@ def test_device_list_leg_rejects_invisible_ordinals(monkeypatch):
     monkeypatch.setenv("FITOCT_BENCH_DEVICE_LIST", "0,3")
     with pytest.raises(ValueError, match="not among the 2 visible"):
         bench._dl_devices(2, 2)
+
+
+def test_dump_outputs_keeps_one_seeded_subset_of_the_chains(tmp_path, monkeypatch):
+    """bench.dump_outputs (``--dump-outputs DIR``): every array as DIR/<name>.npy in
+    float64; above the byte budget the same seeded subset of the chains in every array,
+    listed in chains.npy, the same from call to call."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    arrays = {"draws": rng.standard_normal((37, 5, 3)), "stepsize": rng.random(37),
+              "inv_metric": rng.random((37, 2)).astype(np.float32)}
+    bench.dump_outputs(str(tmp_path / "all"), arrays)
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert np.array_equal(np.load(tmp_path / "all" / "chains.npy"), np.arange(37.0))
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1500)   # 152 bytes per chain: 9 of the 37
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    keep = np.load(tmp_path / "a" / "chains.npy")
+    assert keep.dtype == np.float64 and len(keep) == 9 and np.all(np.diff(keep) > 0)
+    total = 0
+    for f in sorted(os.listdir(tmp_path / "a")):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert np.array_equal(a, b)
+        total += a.nbytes
+        if f != "chains.npy":
+            assert np.array_equal(a, arrays[f[:-4]][keep.astype(int)])
+    assert total <= 1500
