@@ -388,18 +388,15 @@ __device__ __forceinline__ void wave_sum_n(double (&x)[N]) {
 // v_fma_f64 with all three operands in VGPRs.  In the sampler's code the compiler keeps
 // fexp's coefficients in VGPRs (its SGPRs are spent) and forms p * r + c as a copy of c into
 // the destination plus a v_fmac_f64: two VALU instructions per Horner step.  Same operation.
+// Every sampler uses it (the migrating ones too since write_mp's single exp freed their
+// registers; round 3 had to leave them out: profiles/r03_ab_fmav.txt).  The addend in an SGPR
+// pair instead costs the migrating kernels 23-29 more spilled SGPRs for the same speed
+// (profiles/r07_ab_sampler_valu.txt).
 __device__ __forceinline__ double fma_v(double a, double b, double c) {
   double d;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
   return d;
 }
-template <bool V3>
-__device__ __forceinline__ double fmac3(double a, double b, double c) {
-  if constexpr (V3) return fma_v(a, b, c);
-  else return fma(a, b, c);
-}
-// V3: Horner steps as fma_v (the samplers where that form compiles without spills, Chain::FV3)
-template <bool V3 = false>
 __device__ __forceinline__ double fexp(double x) {
   x = fmin(fmax(x, -746.0), 710.0);
   const double SH = 6755399441055744.0;   // 1.5 * 2^52
@@ -409,18 +406,18 @@ __device__ __forceinline__ double fexp(double x) {
   double r = fma(-n, 6.93147180369123816490e-01, x);
   r = fma(-n, 1.90821492927058770002e-10, r);
   double p = 2.08767569878680989792e-09;   // 1/12!
-  p = fmac3<V3>(p, r, 2.50521083854417187751e-08);
-  p = fmac3<V3>(p, r, 2.75573192239858906526e-07);
-  p = fmac3<V3>(p, r, 2.75573192239858906526e-06);
-  p = fmac3<V3>(p, r, 2.48015873015873015873e-05);
-  p = fmac3<V3>(p, r, 1.98412698412698412698e-04);
-  p = fmac3<V3>(p, r, 1.38888888888888888889e-03);
-  p = fmac3<V3>(p, r, 8.33333333333333333333e-03);
-  p = fmac3<V3>(p, r, 4.16666666666666666667e-02);
-  p = fmac3<V3>(p, r, 1.66666666666666666667e-01);
-  p = fmac3<V3>(p, r, 0.5);
-  p = fmac3<V3>(p, r, 1.0);
-  p = fmac3<V3>(p, r, 1.0);
+  p = fma_v(p, r, 2.50521083854417187751e-08);
+  p = fma_v(p, r, 2.75573192239858906526e-07);
+  p = fma_v(p, r, 2.75573192239858906526e-06);
+  p = fma_v(p, r, 2.48015873015873015873e-05);
+  p = fma_v(p, r, 1.98412698412698412698e-04);
+  p = fma_v(p, r, 1.38888888888888888889e-03);
+  p = fma_v(p, r, 8.33333333333333333333e-03);
+  p = fma_v(p, r, 4.16666666666666666667e-02);
+  p = fma_v(p, r, 1.66666666666666666667e-01);
+  p = fma_v(p, r, 0.5);
+  p = fma_v(p, r, 1.0);
+  p = fma_v(p, r, 1.0);
   return ldexp(p, ni);
 }
 // 1/x to <= 1 ulp: v_rcp_f64 and one Newton step (x finite, nonzero)
@@ -443,9 +440,8 @@ __device__ __forceinline__ XF xf_norm(double m, int e) {
   const double f = frexp(m, &k);
   return XF{f, f == 0.0 ? 0 : e + k};
 }
-template <bool V3 = false>
 __device__ __forceinline__ XF xf_exp(double x) {   // exp(x), x <= +inf; -inf -> 0
-  if (x > -700.0 && x < 700.0) return xf_norm(fexp<V3>(x), 0);
+  if (x > -700.0 && x < 700.0) return xf_norm(fexp(x), 0);
   // above 1e8 (an energy drop no trajectory of a finite start reaches) the weight
   // saturates: the exponent stays within int, and so does the exponent difference of
   // two weights in xf_u_below (>= -1.45e9 - 1.45e8)
@@ -454,7 +450,7 @@ __device__ __forceinline__ XF xf_exp(double x) {   // exp(x), x <= +inf; -inf ->
   // an int; the weight is 0 to every digit the merges can resolve
   if (!(x > -1.0e9)) return XF{0.0, 0};
   const double k = floor(x * 1.4426950408889634);   // log2(e)
-  return xf_norm(fexp<V3>(fma(-k, 0.6931471805599453, x)), (int)k);
+  return xf_norm(fexp(fma(-k, 0.6931471805599453, x)), (int)k);
 }
 __device__ __forceinline__ XF xf_add(XF a, XF b) {
   if (a.m == 0.0) return b;
@@ -1067,10 +1063,6 @@ struct Chain {
   // of every leaf (write_mp, finish_grad): same arithmetic, no LDS reads on the
   // NUTS wave's critical path (configs 2 / 5 +2 %).  Not at NNP = 24 (it would spill).
   static constexpr bool KROW = NNP <= 16 && !MIG && MODE_ != MODE_ROWS;
-  // fexp's Horner steps as three-VGPR FMAs (fma_v) in the non-migrating samplers: bitwise
-  // the same, configs 2 / 5 +2 / +0.6 %.  The migrating samplers then spill a VGPR (the
-  // headline horseshoe one loses 2.2 %, profiles/r03_ab_fmav.txt): they keep the compiler's form
-  static constexpr bool FV3 = !MIG;
   double krow[KROW ? NNP : 1];
   const AS_LDS double* bv;
   int lane, slot, lc, gid, nct;
@@ -1245,31 +1237,51 @@ struct Chain {
     for (int s = 0; s < PPL; ++s) qs[idx(s)] = q.a[s];
     wave_order();   // q of every lane visible: the yGP lanes start at once, in parallel with
                     // the constrained values below
-    double yv = 0.0, hl = 0.0, u = 0.0;
-    const int jl = lane < Nn ? lane : 0;
-    if (FAM == FAM_HORSESHOE) {
+    if constexpr (FAM == FAM_HORSESHOE) {
       // Tests/horseShoePrior.stan:30-32 in the exponent: lambda_j tau =
       // r1_l sqrt(r2_l) r1_g sqrt(r2_g) = exp(u1_l + u2_l/2 + u1_g + u2_g/2)
+      // The z_j lanes (3 + j) have no constrained value of their own to form, so lambda_j tau
+      // is evaluated there: one exp per position serves both, each value through the same
+      // function as before, and z_j is the lane's own q.
+      const int j = lane - 3;
+      const bool zl = (unsigned)j < (unsigned)Nn;
+      const int jl = zl ? j : 0;
       const double a1 = qs[5 + Nn + jl], a2 = qs[5 + 2 * Nn + jl];
       const double g1 = qs[3 + Nn], g2 = qs[4 + Nn];
-      u = qs[3 + jl];
-      hl = fexp<FV3>(fma(0.5, a2, a1) + fma(0.5, g2, g1));
-    } else {
-      u = qs[3 + jl];
-    }
+      const double ha = fma(0.5, a2, a1) + fma(0.5, g2, g1);
+      double hl = 0.0;
 #pragma unroll
-    for (int s = 0; s < PPL; ++s) {
-      const int k = idx(s);
-      const double ev = (k < D && is_log(k)) ? fexp<FV3>(q.a[s]) : q.a[s];
-      qe[k] = ev;
-      if (s == 0 && lane < 3) MP[lane] = ev;   // theta for the gradient waves
-    }
-    yv = (FAM == FAM_HORSESHOE) ? u * hl : u;
-    if (lane >= Nn) yv = hl = 0.0;
-    if (lane < NNP) {
-      AUX[lane] = yv;
-      AUX[32 + lane] = hl;
-      if (!poly) MP[4 + lane] = yv;
+      for (int s = 0; s < PPL; ++s) {
+        const int k = idx(s);
+        const double e = fexp((s == 0 && zl) ? ha : q.a[s]);
+        const double ev = (k < D && is_log(k)) ? e : q.a[s];   // (not a z lane's)
+        if (s == 0) hl = zl ? e : 0.0;
+        qe[k] = ev;
+        if (s == 0 && lane < 3) MP[lane] = ev;   // theta for the gradient waves
+      }
+      const double yv = zl ? q.a[0] * hl : 0.0;
+      if ((unsigned)j < (unsigned)NNP) {
+        AUX[j] = yv;
+        AUX[32 + j] = hl;
+        if (!poly) MP[4 + j] = yv;
+      }
+    } else {
+      const int jl = lane < Nn ? lane : 0;
+      const double u = qs[3 + jl];
+#pragma unroll
+      for (int s = 0; s < PPL; ++s) {
+        const int k = idx(s);
+        const double ev = (k < D && is_log(k)) ? fexp(q.a[s]) : q.a[s];
+        qe[k] = ev;
+        if (s == 0 && lane < 3) MP[lane] = ev;   // theta for the gradient waves
+      }
+      double yv = u, hl = 0.0;
+      if (lane >= Nn) yv = hl = 0.0;
+      if (lane < NNP) {
+        AUX[lane] = yv;
+        AUX[32 + lane] = hl;
+        if (!poly) MP[4 + lane] = yv;
+      }
     }
     sub(5, ts);
     if (poly) {  // c_l = b_l (K^-1 yGP)_l ; K^-1 padded to NNP x NNP
@@ -1299,7 +1311,15 @@ struct Chain {
     if (k < 3) return 1 + k;
     if (k == D - 1) return 0;
     if (k < 3 + Nn) return 4 + (k - 3);
-    if (FAM == FAM_HORSESHOE && k >= 5 + Nn) return 4 + ((k - 5 - Nn) % Nn);
+    if (FAM == FAM_HORSESHOE && k >= 5 + Nn) {
+      // local scale j of r1 (k = 5 + Nn + j) or r2 (k = 5 + 2 Nn + j): (k - 5 - Nn) mod Nn on
+      // [0, 2 Nn) without the integer division (~25 VALU instructions per leaf in finish_grad;
+      // x - Nn wraps to a large unsigned value where x < Nn).  Past D (padded lanes; the modulo gave
+      // some 4 + j there) the value is not used: finish_grad forms a gradient only under k < D.
+      if (k >= D) return 0;
+      const unsigned x = (unsigned)(k - 5 - Nn);
+      return 4 + (int)min(x, x - (unsigned)Nn);
+    }
     return 0;
   }
 
@@ -2003,7 +2023,7 @@ struct Chain {
     const V minv = ld(V_MINV);
     double h = -lp + kin(pe, minv);
     if (isnan(h)) h = INFINITY;
-    const XF w = xf_exp<FV3>(Sp->H0 - h);
+    const XF w = xf_exp(Sp->H0 - h);
     Sp->spec_h = h;
     Sp->spec_wm = w.m;
     Sp->spec_we = w.e;
@@ -2241,7 +2261,7 @@ struct Chain {
     double h = -cur_lp + kin(p, minv);
     if (isnan(h)) h = INFINITY;
     const double wl = H0 - h;
-    const XF wleaf = xf_exp<FV3>(wl);
+    const XF wleaf = xf_exp(wl);
     Sp->sub_metro = sub_metro0 + ((wl > 0.0) ? 1.0 : xf_val(wleaf));
     if (h - H0 > 1000.0) {   // divergent: the transition ends here
       Sp->divergent = 1;
@@ -2356,7 +2376,7 @@ struct Chain {
     const V pe = ld(V_CUR_G), minv = ld(V_MINV);   // leaf_spec staged the momentum there
     double h = -Sp->cur_lp + kin(pe, minv);
     if (isnan(h)) h = INFINITY;
-    const XF w = xf_exp<FV3>(Sp->H0 - h);
+    const XF w = xf_exp(Sp->H0 - h);
     Sp->spec_h = h;
     Sp->spec_wm = w.m;
     Sp->spec_we = w.e;
@@ -2539,7 +2559,7 @@ struct Chain {
     if (isnan(h)) h = INFINITY;
     sub(0, ts);
     const double wl = H0 - h;
-    const XF wleaf = xf_exp<FV3>(wl);
+    const XF wleaf = xf_exp(wl);
     // (Stan sums these over the trajectory's leaves in order; here per subtree, then the
     // subtrees' sums in tree order: a reassociation of the same terms, so that two-ended
     // trajectories, whose subtrees are booked by their producers, give the same bits)
