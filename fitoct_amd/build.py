@@ -49,11 +49,13 @@ SOURCES = [
     ("host_model", "host_model.cpp", "g++", ["-O2", "-std=c++17"]),
     ("optimize", "optimize.cpp", "g++", ["-O2", "-std=c++17"]),
     ("stan_output", "stan_output.cpp", "g++", ["-O2", "-std=c++17"]),
+    ("schedule", "schedule.cpp", "g++", ["-O2", "-std=c++17"]),
+    ("stamps_report", "stamps_report.cpp", "g++", ["-O2", "-std=c++17"]),
 ]
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")
-HEADERS = ["kernel_params.h", "philox.h", "host_internal.h", "plan_internal.h"]
+HEADERS = ["kernel_params.h", "philox.h", "host_internal.h", "plan_internal.h", "schedule.h"]
 # FITOCT_HIPFLAGS="-DX=1 ...": extra device-compile flags for A/B variant libraries
 # (built with --force, copied aside, loaded through FITOCT_LIB_PATH)
 EXTRA = os.environ.get("FITOCT_HIPFLAGS", "").split()

@@ -4,11 +4,7 @@
 #include <math.h>
 #include <string.h>
 
-#include <stdio.h>
-#include <stdlib.h>
-
 #include <algorithm>
-#include <climits>
 #include <chrono>
 #include <memory>
 #include <string>
@@ -40,18 +36,10 @@ inline hipError_t launch(bool logp, bool mixed, int bpt, int nnp, const KParams&
     default: return hipErrorInvalidValue;
   }
 }
-int lds_bytes(int ppl, int G, int max_depth);
 int mig_img_words(int ppl);
 }  // namespace fitoct
 
 using namespace fitoct;
-
-#define HIP_TRY(expr)                                                                 \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess)                                                             \
-      return fail(FITOCT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
 
 
 int fitoct::check_init(int C, int D, const double* q, const double* eps, const double* minv) {
@@ -297,9 +285,10 @@ void stage(const fitoct_problem* p, const std::vector<double>& B, const std::vec
   }
 }
 
-// common planning for the sampler and the logp kernel
+// planning common to the sampler and the logp kernel, the data-dependent part: basis mode,
+// bins per lane and the staged data (the launch schedule: schedule.cpp)
 int plan_common(fitoct_plan* pl, const fitoct_problem* p, int chains, int precision, int device,
-                int max_depth, int g_chains = 0, int force_bpt = -1, bool poly_only = false) {
+                const Switches& sw, int force_bpt = -1, bool poly_only = false) {
   int rc = check_problem(p);
   if (rc) return rc;
   int ndev = 0;
@@ -357,7 +346,7 @@ int plan_common(fitoct_plan* pl, const fitoct_problem* p, int chains, int precis
   // layout (y, 1/uy, a in registers; c*x and t formed from the lane's first bin)
   double R16[24];
   if (mode == MODE_POLY && !mono && !pl->mixed && pl->bpt == 0 && p->N <= 16 * GT &&
-      force_bpt < 0 && getenv("FITOCT_NO_GEO") == nullptr &&
+      force_bpt < 0 && !sw.no_geo &&
       geo_ratios(p, pl->nnp, 16, R16)) {
     pl->bpt = 16;
     n_pad = 16 * GT;
@@ -390,7 +379,7 @@ int plan_common(fitoct_plan* pl, const fitoct_problem* p, int chains, int precis
   k.bvec = dk + kinv.size();
   k.N = p->N;
   k.n_pad = n_pad;
-  k.geo = (mode == MODE_POLY && !mono && !pl->mixed && getenv("FITOCT_NO_GEO") == nullptr)
+  k.geo = (mode == MODE_POLY && !mono && !pl->mixed && !sw.no_geo)
               ? geo_ratios(p, pl->nnp, pl->bpt, k.geo_R) : 0;
   if (pl->bpt == 16) {
     if (!k.geo) return fail(FITOCT_E_INTERNAL, "16-bin layout without a geometric grid");
@@ -417,35 +406,12 @@ int plan_common(fitoct_plan* pl, const fitoct_problem* p, int chains, int precis
   k.sigma_scale_inv = 1.0 / p->sigma_scale;
   k.theta_rate = p->theta_prior == 1 ? 1.0 / p->lambda_scale : 0.0;
   k.chains = chains;
-
-  // chains per tile: fill every CU with one tile first, then stack chains
-  const int ncu = std::max(1, prop.multiProcessorCount);
-  pl->ncu = ncu;
-  // (a batch plans every problem's tiles from the batch's total chain count)
-  const int gc = g_chains > 0 ? g_chains : chains;
-  int G = std::max(1, std::min(GMAX, (gc + ncu - 1) / ncu));
-  // (the kernel's static LDS comes on top of the carve: STATIC_LDS_RESERVE)
-  while (G > 1 && lds_bytes(pl->ppl, G, max_depth) > 160 * 1024 - STATIC_LDS_RESERVE) --G;
-  if (lds_bytes(pl->ppl, G, max_depth) > 160 * 1024 - STATIC_LDS_RESERVE)
-    return fail(FITOCT_E_ARG, "max_treedepth too large for the LDS budget");
-  k.G = G;
-  k.max_depth = max_depth;
-  k.spec = 0;   // set below, once migration is decided
-  pl->tiles = (chains + G - 1) / G;
-  pl->lds = lds_bytes(pl->ppl, G, max_depth);
+  pl->ncu = std::max(1, prop.multiProcessorCount);
   return FITOCT_OK;
 }
 
-int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, int g_chains,
-                int force_bpt, fitoct_plan** out, bool poly_only = false);
-
-// Migrating tiles of several chains speculate once they host <= this many live chains.
-// Measured on config 3 at full length (profiles/r03_ab_spec_live.txt, two interleaved
-// runs each): 0 (no speculation) 119.1 k draws/s, 1: 119.7-120.2 k, 2: 121.2-121.4 k,
-// 3: 121.5-122.0 k, 4 (always): 119.5-120.3 k.  Tiles that do not migrate (batch mode,
-// config 5) lose 7 % with any tail speculation (the speculative kernel's extra registers
-// and per-leaf policy read), so they do not speculate.
-constexpr int kSpecLiveMigrating = 3;
+int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, const Switches& sw,
+                int g_chains, int force_bpt, fitoct_plan** out, bool poly_only = false);
 
 void free_plan(fitoct_plan* pl) {
   if (!pl) return;
@@ -461,8 +427,7 @@ void free_plan(fitoct_plan* pl) {
   (void)hipFree(pl->d_mig);
   (void)hipFree(pl->d_mig_img);
   (void)hipFree(pl->d_stamps);
-  (void)hipFree(pl->d_pair_hdr);
-  (void)hipFree(pl->d_pair_buf);
+  pl->pairs.free();
   if (pl->h_prog) (void)hipHostFree(pl->h_prog);
   if (pl->h_cancel) (void)hipHostFree(pl->h_cancel);
   if (pl->ev0) (void)hipEventDestroy(pl->ev0);
@@ -572,8 +537,14 @@ int32_t fitoct_evaluator_create(const fitoct_problem* prob, int32_t capacity, in
                                                                        fitoct_evaluator_destroy);
     fitoct_evaluator* ev = guard.get();
     ev->pl = new fitoct_plan();
-    int rc = plan_common(ev->pl, prob, capacity, precision, device, 0);
+    const Switches sw = Switches::from_env();
+    int rc = plan_common(ev->pl, prob, capacity, precision, device, sw);
     ev->pl->cfg.device = device;
+    if (!rc) {   // the logp kernel takes the schedule's chains (points) per tile, nothing else
+      const fitoct_plan* pl = ev->pl;
+      ev->pl->sched = choose_schedule(pl->ppl, pl->kp.mode, capacity, 0, pl->ncu, 0, sw, &rc);
+      ev->pl->kp.G = ev->pl->sched.G;
+    }
     auto run = [&]() -> int {
       if (rc) return rc;
       const int D = ev->pl->kp.D;
@@ -611,12 +582,11 @@ int32_t fitoct_evaluator_run(fitoct_evaluator* ev, int32_t n, const double* q, i
       k.chains = n;
       k.lp_out = ev->d_out + (size_t)n * D;
       k.s2_out = k.lp_out + n;
-      pl->tiles = (n + k.G - 1) / k.G;
       HIP_TRY(hipMemcpy(pl->d_kp, &k, sizeof(KParams), hipMemcpyHostToDevice));
       ev->cur_n = n;
     }
     HIP_TRY(hipMemcpy(ev->d_q, q, sizeof(double) * (size_t)n * D, hipMemcpyHostToDevice));
-    HIP_TRY(launch(true, pl->mixed, pl->bpt, pl->nnp, k, pl->d_kp, pl->tiles, 0));
+    HIP_TRY(launch(true, pl->mixed, pl->bpt, pl->nnp, k, pl->d_kp, (n + k.G - 1) / k.G, 0));
     // one copy back of grad | lp | sumr2 (contiguous)
     ev->host.resize((size_t)n * (D + 2));
     HIP_TRY(hipMemcpy(ev->host.data(), ev->d_out, sizeof(double) * ev->host.size(),
@@ -677,44 +647,46 @@ int32_t fitoct_plan_create(const fitoct_problem* prob, const fitoct_config* cfg,
     fitoct_config c = *cfg;
     c.device = devs[0];
     c.n_devices = 0;
-    return plan_create(prob, &c, 0, -1, out);
+    return plan_create(prob, &c, Switches::from_env(), 0, -1, out);
   });
 }
 
 }  // extern "C"
 
-namespace {
-// Paired tiles (nuts_device.hip "paired tiles"): a launch of one-chain tiles with two-ended
-// trajectories whose 2 x tiles (in whole groups of 8 + 8 blocks) fit on the chip grows each
-// trajectory's forward end in a partner tile with its own gradient waves, instead of sharing
-// the tile's.  Same draws bit for bit: the partner runs the same producer on the same values.
-// A partner that does not get a CU at launch leaves its primary to grow both ends (the pair's
-// hand-shake), so this is safe on a shared GPU too.  FITOCT_NO_PAIR=1: off.
-bool want_pairs(const KParams& k, int tiles, int ncu) {
-  if (!(k.bidi && k.G == 1 && pair_grid(tiles) <= ncu) || getenv("FITOCT_NO_PAIR") != nullptr)
-    return false;
-  // with the basis rows (N <= 512) an unpaired tile is faster (its chain's wave books the
-  // forward end: config 2 253 k vs 245 k draws/s, profiles/r06_ab_unpaired.txt), so there the
-  // pairing is on only with FITOCT_PAIR=1
-  return k.mode == MODE_POLY || getenv("FITOCT_PAIR") != nullptr;
-}
-// the pairs' hand-off words and buffers for `tiles` tiles; sets every k.pair_* but the count
-int alloc_pairs(KParams& k, int tiles, int ppl, int** hdr, double** buf) {
-  k.pair = 1;
-  k.pair_tiles = tiles;
+int fitoct::PairBuffers::alloc(int tiles_, int ppl, const Switches& sw) {
+  tiles = tiles_;
   // the start (q, p, g, minv + scalars), then two subtree record slots (5 vectors + 16 scalars)
-  k.pair_stride = (PAIR_START_DOUBLES + WAVE * ppl * 4 + 2 * (WAVE * ppl * 5 + 16) + 15) / 16 * 16;
-  HIP_TRY(hipMalloc(hdr, sizeof(int) * PAIR_HDR_INTS * (size_t)tiles));
-  HIP_TRY(hipMalloc(buf, sizeof(double) * (size_t)k.pair_stride * tiles));
-  k.pair_hdr = *hdr;
-  k.pair_buf = *buf;
-  const char* t = getenv("FITOCT_TEST_PAIR_ABSENT");   // test hook: partners never join
-  k.pair_test_absent = (t && atoi(t) != 0) ? 1 : 0;
+  stride = (PAIR_START_DOUBLES + WAVE * ppl * 4 + 2 * (WAVE * ppl * 5 + 16) + 15) / 16 * 16;
+  test_absent = sw.test_pair_absent ? 1 : 0;
+  HIP_TRY(hipMalloc(&hdr, sizeof(int) * PAIR_HDR_INTS * (size_t)tiles));
+  HIP_TRY(hipMalloc(&buf, sizeof(double) * (size_t)stride * tiles));
   return FITOCT_OK;
 }
+void fitoct::PairBuffers::apply(KParams& k) const {
+  k.pair = 1;
+  k.pair_tiles = tiles;
+  k.pair_stride = stride;
+  k.pair_test_absent = test_absent;
+  k.pair_hdr = hdr;
+  k.pair_buf = buf;
+}
+int fitoct::PairBuffers::zero(hipStream_t st) const {
+  HIP_TRY(hipMemsetAsync(hdr, 0, sizeof(int) * PAIR_HDR_INTS * (size_t)tiles, st));
+  return FITOCT_OK;
+}
+void fitoct::PairBuffers::free() {
+  (void)hipFree(hdr);
+  (void)hipFree(buf);
+  hdr = nullptr;
+  buf = nullptr;
+}
 
-int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, int g_chains,
-                int force_bpt, fitoct_plan** out, bool poly_only) {
+namespace {
+
+// A plan: check the config, plan the data (plan_common), choose the launch schedule
+// (schedule.cpp), allocate what it asks for and copy it into the kernel's parameters.
+int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, const Switches& sw,
+                int g_chains, int force_bpt, fitoct_plan** out, bool poly_only) {
   if (!out) return fail(FITOCT_E_ARG, "out is NULL");
   *out = nullptr;
   if (!cfg) return fail(FITOCT_E_ARG, "config is NULL");
@@ -728,11 +700,25 @@ int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, int g_chai
   // released on every early return or exception until handed to the caller
   std::unique_ptr<fitoct_plan, void (*)(fitoct_plan*)> guard(new fitoct_plan(), free_plan);
   fitoct_plan* pl = guard.get();
-  int rc = plan_common(pl, prob, cfg->chains, cfg->precision, cfg->device, cfg->max_treedepth,
-                       g_chains, force_bpt, poly_only);
+  int rc = plan_common(pl, prob, cfg->chains, cfg->precision, cfg->device, sw, force_bpt,
+                       poly_only);
   if (rc) return rc;
   pl->cfg = *cfg;
+  pl->sw = sw;
   KParams& k = pl->kp;
+  // (a batch plans every problem's tiles from the batch's total chain count, and pairs its
+  // tiles itself: fitoct_batch_create)
+  pl->sched = choose_schedule(pl->ppl, k.mode, cfg->chains, g_chains, pl->ncu, cfg->max_treedepth,
+                              sw, &rc);
+  if (rc) return rc;
+  const Schedule& sc = pl->sched;
+  k.G = sc.G;
+  k.spec_live = sc.spec_live;
+  k.spec = sc.spec;
+  k.bidi = sc.bidi;
+  k.tail_bidi = sc.tail_bidi;
+  k.tail_left = sc.tail_left;
+  k.tail_idle_ticks = sc.tail_idle_ticks;
   const int C = cfg->chains, D = k.D;
   k.chain_offset = cfg->chain_offset;
   k.warmup = cfg->warmup;
@@ -758,7 +744,7 @@ int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, int g_chai
   const int vlen = WAVE * pl->ppl;
   auto setup = [&]() -> int {
     // proposal pools: the chains', then the two-ended producers' (GMAX per tile; produce)
-    const size_t pools = (size_t)C + (size_t)GMAX * ((C + pl->kp.G - 1) / pl->kp.G);
+    const size_t pools = (size_t)C + (size_t)GMAX * sc.tiles;
     HIP_TRY(hipMalloc(&pl->d_stack, sizeof(double) * pools * (cfg->max_treedepth + 1) * POOL_VECS * vlen));
     HIP_TRY(hipMalloc(&pl->d_fin, sizeof(double) * (size_t)C * (1 + 2 * D)));
     HIP_TRY(hipMalloc(&pl->d_status, sizeof(int) * C));
@@ -796,12 +782,8 @@ int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, int g_chai
     rc = prog_setup();
     if (rc) return rc;
   }
-  // Chain migration (work balance): only when every tile of the launch is
-  // co-resident (one tile per CU), so an idle tile waiting for a migrant never
-  // keeps a pending tile off the chip; off in batch mode (a tile holds one
-  // problem's bins) and with FITOCT_NO_MIGRATE.
-  if (g_chains == 0 && k.G >= 2 && pl->tiles <= pl->ncu && getenv("FITOCT_NO_MIGRATE") == nullptr) {
-    const int T = pl->tiles, words = mig_img_words(pl->ppl);
+  if (sc.migrate) {   // the migration control block and the chain images in flight
+    const int T = sc.tiles, words = mig_img_words(pl->ppl);
     pl->mig_bytes = sizeof(int) * (MIG_HDR + 2 * (size_t)T + (size_t)T * GMAX);
     auto mig_setup = [&]() -> int {
       HIP_TRY(hipMalloc(&pl->d_mig, pl->mig_bytes));
@@ -815,55 +797,10 @@ int plan_create(const fitoct_problem* prob, const fitoct_config* cfg, int g_chai
     k.mig_tiles = T;
     k.mig_img_words = words;
   }
-  // Speculative leaves (nuts_device.hip leaf_spec).  A tile of one (two) chain(s) always
-  // speculates, with a spare NUTS wave helping each chain (config 2 +4 %).  A tile of several chains
-  // has no spare wave: while it hosts 4 live chains the sweep hides the sampler's latency
-  // and speculation only adds work, so a migrating chain speculates only once its tile has
-  // thinned out to <= kSpecLiveMigrating chains (the launch's tail, config 3 +2 %).  Draws
-  // are the same bit for bit either way.  FITOCT_SPEC_LIVE=n overrides spec_live (0: never; GMAX:
-  // always), FITOCT_SPEC=1 is FITOCT_SPEC_LIVE=GMAX (tests), FITOCT_NO_SPEC=1 builds the
-  // plain sampler.
-  {
-    // (tiles of two chains without migration -- a batch of 257..512 chains, config 5's
-    // per-GPU share at 2 GPUs -- have a spare NUTS wave per chain too: deep speculation)
-    int live = pl->mig_bytes > 0 ? kSpecLiveMigrating : k.G <= 2 ? 1 : 0;
-    if (const char* fs = getenv("FITOCT_SPEC")) live = atoi(fs) != 0 ? GMAX : live;
-    if (const char* fl = getenv("FITOCT_SPEC_LIVE")) live = atoi(fl);
-    if (getenv("FITOCT_NO_SPEC") != nullptr) live = 0;
-    k.spec_live = std::max(0, std::min(live, GMAX));
-    k.spec = k.spec_live > 0 ? 1 : 0;
-  }
-  // Two-ended trajectories (nuts_device.hip): tiles of one chain grow the trajectory's two
-  // ends at once -- two spare NUTS waves build the subtrees of each direction whole, each in a
-  // chain area of its own, and the chain's wave books the trajectory level from one record per
-  // subtree.  Same draws bit for bit.  The three chain areas must fit, else the tile stays on
-  // the one-ended path (at Nn 16..24 a chain area holds two parameters per lane: three of
-  // them at max_treedepth 10 take ~181 KB of the 160 KB).  FITOCT_NO_BIDI=1: off.
-  k.bidi = 0;
-  if (k.spec && k.G == 1 && pl->mig_bytes == 0 && getenv("FITOCT_NO_BIDI") == nullptr) {
-    const int base = lds_bytes(pl->ppl, 3, k.max_depth);
-    if (base <= 160 * 1024 - STATIC_LDS_RESERVE) {
-      k.bidi = 1;
-      pl->lds = base;
-    }
-  }
-  // Two-ended trajectories in the tail of a migrating launch (nuts_device.hip receive_chain):
-  // the producers are idle receivers of the tile (their own chain areas: no LDS added).  Same
-  // draws bit for bit.  FITOCT_NO_TAIL_BIDI=1: off; FITOCT_TAIL_LEFT=n: start at n unfinished
-  // chains (default: every chain of the launch -- a chain alone in its tile goes two-ended
-  // whenever two receivers are idle; one per tile measured 1 % slower on config 3).
-  k.tail_bidi = 0;
-  if (pl->mig_bytes > 0 && k.spec && getenv("FITOCT_NO_TAIL_BIDI") == nullptr) {
-    k.tail_bidi = 1;
-    k.tail_left = k.chains;   // from the start (config 3: +1.0 % over one per tile, profiles/r05_ab_tail_left.txt)
-    if (const char* e = getenv("FITOCT_TAIL_LEFT")) k.tail_left = std::max(0, atoi(e));
-    if (const char* e = getenv("FITOCT_TEST_TAIL_IDLE_US"))   // test hook: producers give up early
-      k.tail_idle_ticks = 100ULL * (unsigned long long)std::max(1, atoi(e));
-  }
-  // (a batch pairs its tiles itself: fitoct_batch_create)
-  if (g_chains == 0 && want_pairs(k, pl->tiles, pl->ncu)) {
-    rc = alloc_pairs(k, pl->tiles, pl->ppl, &pl->d_pair_hdr, &pl->d_pair_buf);
+  if (sc.pair) {
+    rc = pl->pairs.alloc(sc.tiles, pl->ppl, sw);
     if (rc) return rc;
+    pl->pairs.apply(k);
   }
   *out = guard.release();
   return FITOCT_OK;
@@ -880,23 +817,21 @@ int32_t fitoct_plan_get_info(const fitoct_plan* pl, fitoct_plan_info* info) {
     info->n_cols = pl->kp.ncols;
     info->iters_saved = pl->kp.iters_saved;
     info->chains = pl->kp.chains;
-    info->tiles = pl->tiles;
-    info->chains_per_tile = pl->kp.G;
-    info->sampler = pl->mig_bytes > 0
-                        ? (pl->kp.spec ? FITOCT_SAMPLER_MIGRATE_SPEC : FITOCT_SAMPLER_MIGRATE)
-                    : pl->kp.spec ? FITOCT_SAMPLER_SPECULATIVE : FITOCT_SAMPLER_PLAIN;
+    const Schedule& sc = pl->sched;
+    info->tiles = sc.tiles;
+    info->chains_per_tile = sc.G;
+    info->sampler = sc.sampler;
     info->n_devices = 1;
     info->bins_per_thread = pl->bpt;
     info->threads_per_tile = TPB;
-    info->lds_bytes = pl->lds;
+    info->lds_bytes = sc.lds;
     info->n_pad = pl->kp.n_pad;
     info->draws_bytes = (int64_t)pl->draws_bytes;
-    const bool te = pl->kp.bidi || pl->kp.tail_bidi;
-    info->two_ended = pl->kp.bidi ? 1 : pl->kp.tail_bidi ? 2 : 0;
-    info->ring_records = te ? 1 : 0;   // (ABI 7: one subtree record per end)
+    info->two_ended = sc.bidi ? 1 : sc.tail_bidi ? 2 : 0;
+    info->ring_records = info->two_ended ? 1 : 0;   // (ABI 7: one subtree record per end)
     info->ring_records_in_levels = 0;
-    info->paired = pl->kp.pair;
-    info->workgroups = pl->grid();
+    info->paired = sc.pair ? 1 : 0;
+    info->workgroups = sc.grid;
     info->basis_mode = pl->kp.mode;
     return FITOCT_OK;
   });
@@ -950,19 +885,20 @@ int32_t fitoct_plan_launch(fitoct_plan* pl, void* d_draws, void* stream) {
     HIP_TRY(hipMemsetAsync(pl->d_status, 0, sizeof(int) * k.chains, st));
     HIP_TRY(hipMemsetAsync(k.bidi_count, 0, 2 * sizeof(long long), st));   // + pair_count
     if (pl->d_mig) HIP_TRY(hipMemsetAsync(pl->d_mig, 0, pl->mig_bytes, st));
-    if (k.pair)   // every word the pairs poll: zero before every launch
-      HIP_TRY(hipMemsetAsync(k.pair_hdr, 0, sizeof(int) * PAIR_HDR_INTS * (size_t)k.pair_tiles, st));
-    const bool want_stamps = getenv("FITOCT_STAMPS") != nullptr;   // diagnostic only
-    if (want_stamps) {
-      if (!pl->d_stamps) HIP_TRY(hipMalloc(&pl->d_stamps, sizeof(long long) * NSTAMP * pl->tiles));
-      HIP_TRY(hipMemsetAsync(pl->d_stamps, 0, sizeof(long long) * NSTAMP * pl->tiles, st));
+    if (pl->pairs.on()) {
+      const int rc = pl->pairs.zero(st);
+      if (rc) return rc;
+    }
+    if (stamps_requested(&k.bench_sweeps)) {   // diagnostic only
+      const size_t bytes = sizeof(long long) * NSTAMP * pl->sched.tiles;
+      if (!pl->d_stamps) HIP_TRY(hipMalloc(&pl->d_stamps, bytes));
+      HIP_TRY(hipMemsetAsync(pl->d_stamps, 0, bytes, st));
       k.stamps = pl->d_stamps;
-      k.bench_sweeps = getenv("FITOCT_BENCH_SWEEPS") ? atoi(getenv("FITOCT_BENCH_SWEEPS")) : 0;
     }
     HIP_TRY(hipEventRecord(pl->ev0, st));
     if (!pl->d_kp) HIP_TRY(hipMalloc(&pl->d_kp, sizeof(KParams)));
     HIP_TRY(hipMemcpyAsync(pl->d_kp, &k, sizeof(KParams), hipMemcpyHostToDevice, st));
-    HIP_TRY(launch(false, pl->mixed, pl->bpt, pl->nnp, k, pl->d_kp, pl->grid(), st));
+    HIP_TRY(launch(false, pl->mixed, pl->bpt, pl->nnp, k, pl->d_kp, pl->sched.grid, st));
     HIP_TRY(hipEventRecord(pl->ev1, st));
     pl->last_draws = dst;
     pl->launched = true;
@@ -1016,154 +952,10 @@ int32_t fitoct_plan_wait(fitoct_plan* pl) {
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, pl->ev0, pl->ev1));
     pl->kernel_ms = ms;
-    if (pl->d_stamps && getenv("FITOCT_STAMPS") != nullptr) {
-      std::vector<long long> h((size_t)NSTAMP * pl->tiles);
+    if (pl->d_stamps && stamps_requested(nullptr)) {
+      std::vector<long long> h((size_t)NSTAMP * pl->sched.tiles);
       HIP_TRY(hipMemcpy(h.data(), pl->d_stamps, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-      double steps = 0, tg = 0, tn = 0, tt = 0, smax = 0, tw = 0, nw = 0, tsw = 0, tno = 0;
-      double ts0 = 0, ts1 = 0;
-      double act_t[18] = {0}, act_n[18] = {0};
-      for (int t = 0; t < pl->tiles; ++t) {
-        const long long* o = h.data() + (size_t)NSTAMP * t;
-        steps += o[0];
-        tg += o[1];
-        tn += o[2];
-        tt += o[3];
-        tw += o[40];
-        nw += o[41];
-        tsw += o[42];
-        tno += o[43];
-        ts0 += o[44];
-        ts1 += o[45];
-        smax = std::max(smax, (double)o[0]);
-        for (int a = 0; a < 18; ++a) {
-          act_t[a] += o[4 + a];
-          act_n[a] += o[22 + a];
-        }
-      }
-      double subt[12] = {0}, wb[8] = {0};
-      for (int t = 0; t < pl->tiles; ++t) {
-        for (int k = 0; k < 8; ++k) subt[k] += h[(size_t)NSTAMP * t + 48 + k];
-        for (int k = 0; k < 4; ++k) subt[8 + k] += h[(size_t)NSTAMP * t + 68 + k];
-        for (int k = 0; k < 8; ++k) wb[k] += h[(size_t)NSTAMP * t + 56 + k];
-      }
-      fprintf(stderr, "[fitoct stamps] gradient-wave busy per sweep by wave:");
-      for (int k = 0; k < 8; ++k) fprintf(stderr, " %.0f", wb[k] / std::max(steps, 1.0));
-      fprintf(stderr, "\n");
-      // per gradient of chain 0 (act_n[1]: A_GRAD runs); a11 is the speculative path's
-      // separate bookkeeping action (A_SPEC_BOOK)
-      fprintf(stderr, "[fitoct stamps] sub-action cycles per gradient (chain 0): ");
-      for (int k = 0; k < 12; ++k)
-        if (subt[k] > 0) fprintf(stderr, "s%d:%.0f ", k, subt[k] / std::max(act_n[1], 1.0));
-      fprintf(stderr, "\n");
-      fprintf(stderr, "[fitoct stamps] per action (chain 0 of each tile): ");
-      for (int a = 1; a < 18; ++a)
-        if (act_n[a] > 0) fprintf(stderr, "a%d:%.0fx%.0f ", a, act_n[a] / pl->tiles, act_t[a] / act_n[a]);
-      fprintf(stderr, "\n");
-      fprintf(stderr,
-              "[fitoct stamps] tiles=%d mean sweeps/tile=%.0f max=%.0f | per sweep: grad-wave busy %.0f "
-              "nuts-wave busy %.0f wall %.0f memtime ticks\n",
-              pl->tiles, steps / pl->tiles, smax, tg / steps, tn / steps, tt / steps);
-      fprintf(stderr,
-              "[fitoct stamps] chain 0 per NUTS round: busy %.0f, waiting for its gradient %.0f "
-              "(enqueue->sweep done %.0f, sweep done->resumed %.0f)\n",
-              tn / std::max(nw, 1.0), tw / std::max(nw, 1.0), tsw / std::max(nw, 1.0),
-              tno / std::max(nw, 1.0));
-      fprintf(stderr, "[fitoct stamps] enqueue -> first wave starts %.0f, last wave starts %.0f\n",
-              ts0 / std::max(nw, 1.0), ts1 / std::max(nw, 1.0));
-      // tile timeline on the 100 MHz clock: how much of the launch the tiles sit idle at
-      // the end (the kernel ends with its last tile)
-      {
-        long long t0 = LLONG_MAX, t1 = 0;
-        std::vector<double> ends, firsts;
-        for (int t = 0; t < pl->tiles; ++t) {
-          const long long* o = h.data() + (size_t)NSTAMP * t;
-          t0 = std::min(t0, o[64]);
-          t1 = std::max(t1, o[65]);
-        }
-        const double span = std::max(1.0, (double)(t1 - t0));
-        double done_sum = 0;
-        for (int t = 0; t < pl->tiles; ++t) {
-          const long long* o = h.data() + (size_t)NSTAMP * t;
-          ends.push_back((o[65] - t0) / span);
-          if (o[66] > 0) firsts.push_back((o[66] - t0) / span);
-          done_sum += o[67];
-        }
-        std::sort(ends.begin(), ends.end());
-        std::sort(firsts.begin(), firsts.end());
-        auto q = [](const std::vector<double>& v, double f) {
-          return v.empty() ? 0.0 : v[std::min(v.size() - 1, (size_t)(f * (v.size() - 1)))];
-        };
-        double mean_end = 0;
-        for (double e : ends) mean_end += e;
-        mean_end /= std::max<size_t>(1, ends.size());
-        fprintf(stderr,
-                "[fitoct stamps] tile ends (fraction of the launch): mean %.3f p10 %.3f p50 %.3f "
-                "p90 %.3f | first chain done in a tile: p10 %.3f p50 %.3f p90 %.3f | chains "
-                "finished %.0f, launch %.1f ms\n",
-                mean_end, q(ends, 0.1), q(ends, 0.5), q(ends, 0.9), q(firsts, 0.1), q(firsts, 0.5),
-                q(firsts, 0.9), done_sum, span / 1e5);
-        // tile occupancy: share of all tiles' time, and of all sweeps, spent while a tile
-        // hosted k live chains (k = 0..4; the launch's tail runs thinned-out tiles)
-        double ot[5] = {0}, on[5] = {0}, st = 0, sn = 0;
-        for (int t = 0; t < pl->tiles; ++t)
-          for (int k = 0; k < 5; ++k) {
-            ot[k] += h[(size_t)NSTAMP * t + 72 + k];
-            on[k] += h[(size_t)NSTAMP * t + 77 + k];
-          }
-        for (int k = 0; k < 5; ++k) {
-          st += ot[k];
-          sn += on[k];
-        }
-        fprintf(stderr, "[fitoct stamps] tile occupancy (live chains k: share of tile time / of sweeps):");
-        for (int k = 0; k < 5; ++k)
-          fprintf(stderr, " k=%d %.4f/%.4f", k, ot[k] / std::max(st, 1.0), on[k] / std::max(sn, 1.0));
-        fprintf(stderr, "\n");
-      }
-      if (pl->kp.bidi) {   // two-ended roles (tiles of one chain; paired: the forward end's
-                           // producer runs in the partner tile)
-        double hb = 0, hw = 0, hn = 0, hi = 0, pe[2][4] = {{0}};
-        for (int t = 0; t < pl->tiles; ++t) {
-          const long long* o = h.data() + (size_t)NSTAMP * t;
-          hb += o[84];
-          hw += o[85];
-          hn += o[86];
-          hi += o[87];
-          for (int s = 0; s < 2; ++s)
-            for (int k = 0; k < 4; ++k) pe[s][k] += o[88 + 4 * s + k];
-        }
-        fprintf(stderr,
-                "[fitoct stamps] booking wave per booked leaf: busy %.0f, waiting for its record %.0f "
-                "(leaves booked per tile %.0f, idle between trees %.0f per tile)\n",
-                hb / std::max(hn, 1.0), hw / std::max(hn, 1.0), hn / pl->tiles, hi / pl->tiles);
-        for (int s = 0; s < 2; ++s)
-          fprintf(stderr,
-                  "[fitoct stamps] producer of end %d per produced leaf: waiting for its sweep %.0f, "
-                  "for lookahead / record slot %.0f, in trees %.0f (leaves per tile %.0f)\n",
-                  s, pe[s][0] / std::max(pe[s][2], 1.0), pe[s][1] / std::max(pe[s][2], 1.0),
-                  pe[s][3] / std::max(pe[s][2], 1.0), pe[s][2] / pl->tiles);
-        for (int s = 0; s < 2; ++s) {
-          double q[4] = {0, 0, 0, 0}, n = 0;
-          for (int t = 0; t < pl->tiles; ++t) {
-            for (int k = 0; k < 4; ++k) q[k] += h[(size_t)NSTAMP * t + 100 + 4 * s + k];
-            n += h[(size_t)NSTAMP * t + 90 + 4 * s];
-          }
-          fprintf(stderr,
-                  "[fitoct stamps] producer of end %d per leaf (helped): finish_grad %.0f, stage %.0f, "
-                  "hand-over %.0f, prior_part %.0f\n", s, q[0] / std::max(n, 1.0),
-                  q[1] / std::max(n, 1.0), q[2] / std::max(n, 1.0), q[3] / std::max(n, 1.0));
-        }
-        double hb2[2] = {0, 0}, hn2[2] = {0, 0};
-        for (int t = 0; t < pl->tiles; ++t)
-          for (int r = 0; r < 2; ++r) {
-            hb2[r] += h[(size_t)NSTAMP * t + 96 + 2 * r];
-            hn2[r] += h[(size_t)NSTAMP * t + 97 + 2 * r];
-          }
-        for (int r = 0; r < 2; ++r)
-          if (hn2[r] > 0)
-            fprintf(stderr,
-                    "[fitoct stamps] booking helper (%s tile): %.0f cycles per booked leaf, %.0f "
-                    "leaves per tile\n", r ? "partner" : "primary", hb2[r] / hn2[r], hn2[r] / pl->tiles);
-      }
+      report_stamps(h.data(), pl->sched.tiles, pl->sched.bidi != 0);
     }
     pl->ran = true;
     return FITOCT_OK;
@@ -1289,8 +1081,7 @@ void free_batch(fitoct_batch* b) {
   for (fitoct_plan* pl : b->plans) free_plan(pl);
   (void)hipFree(b->d_kp);
   (void)hipFree(b->d_map);
-  (void)hipFree(b->d_pair_hdr);
-  (void)hipFree(b->d_pair_buf);
+  b->pairs.free();
   (void)hipFree(b->d_draws);
   if (b->ev0) (void)hipEventDestroy(b->ev0);
   if (b->ev1) (void)hipEventDestroy(b->ev1);
@@ -1323,6 +1114,7 @@ int32_t fitoct_batch_create(const fitoct_problem* probs, int32_t n_problems,
     b->cfg.device = devs[0];
     b->cfg.n_devices = 0;
     b->n_problems = n_problems;
+    b->sw = Switches::from_env();
     const int C = cfg->chains;
     // one basis mode for the whole batch: resident rows only if every problem has N <= 512
     bool poly_only = false;
@@ -1335,7 +1127,7 @@ int32_t fitoct_batch_create(const fitoct_problem* probs, int32_t n_problems,
         fitoct_config c = b->cfg;
         c.chain_offset = cfg->chain_offset + p * C;
         fitoct_plan* pl = nullptr;
-        const int rc = plan_create(&probs[p], &c, n_problems * C, -1, &pl, poly_only);
+        const int rc = plan_create(&probs[p], &c, b->sw, n_problems * C, -1, &pl, poly_only);
         if (rc) return fail(rc, "problem " + std::to_string(p) + ": " + fitoct_last_error());
         b->plans.push_back(pl);
       }
@@ -1359,7 +1151,8 @@ int32_t fitoct_batch_create(const fitoct_problem* probs, int32_t n_problems,
           c.chain_offset = cfg->chain_offset + (int)p * C;
           free_plan(pl);
           b->plans[p] = nullptr;
-          const int rc = plan_create(&probs[p], &c, n_problems * C, to, &b->plans[p], poly_only);
+          const int rc = plan_create(&probs[p], &c, b->sw, n_problems * C, to, &b->plans[p],
+                                     poly_only);
           if (rc) return rc;
         }
         return FITOCT_OK;
@@ -1382,13 +1175,10 @@ int32_t fitoct_batch_create(const fitoct_problem* probs, int32_t n_problems,
       HIP_TRY(hipMemcpy(b->d_map, map.data(), sizeof(int) * map.size(), hipMemcpyHostToDevice));
       HIP_TRY(hipMalloc(&b->d_kp, sizeof(KParams) * n_problems));
       // paired tiles over the whole batch (one-chain tiles: config 5's 4- and 8-GPU shares)
-      {
-        KParams kq = b->plans[0]->kp;
-        if (want_pairs(kq, b->tiles, b->plans[0]->ncu)) {
-          const int rc2 = alloc_pairs(kq, b->tiles, b->plans[0]->ppl, &b->d_pair_hdr, &b->d_pair_buf);
-          if (rc2) return rc2;
-          b->pair_stride = kq.pair_stride;
-        }
+      const fitoct_plan* q0 = b->plans[0];
+      if (want_pairs(q0->sched, q0->kp.mode, b->tiles, q0->ncu, b->sw)) {
+        const int rc2 = b->pairs.alloc(b->tiles, q0->ppl, b->sw);
+        if (rc2) return rc2;
       }
       // cancellation flag (set by the multi-device layer when another device fails)
       HIP_TRY(hipHostMalloc((void**)&b->h_cancel, sizeof(int),
@@ -1414,8 +1204,8 @@ int32_t fitoct_batch_get_info(const fitoct_batch* b, fitoct_plan_info* info) {
     if (rc) return rc;
     info->chains = b->cfg.chains * (int)b->plans.size();
     info->tiles = b->tiles;
-    info->paired = b->d_pair_hdr ? 1 : 0;
-    info->workgroups = b->d_pair_hdr ? pair_grid(b->tiles) : b->tiles;
+    info->paired = b->pairs.on() ? 1 : 0;
+    info->workgroups = b->grid();
     info->basis_mode = b->plans.empty() ? 0 : b->plans[0]->kp.mode;
     info->draws_bytes = (int64_t)(b->per_bytes * b->plans.size());
     return FITOCT_OK;
@@ -1442,23 +1232,17 @@ int fitoct::batch_run_single(fitoct_batch* b, void* d_draws, void* stream) {
       pl->last_draws = kp[p].draws;
       HIP_TRY(hipMemsetAsync(pl->d_status, 0, sizeof(int) * pl->kp.chains, st));
       HIP_TRY(hipMemsetAsync(pl->kp.bidi_count, 0, 2 * sizeof(long long), st));   // + pair_count
-      if (b->d_pair_hdr) {   // paired tiles: every problem's block names the batch's pairs
-        kp[p].pair = 1;
-        kp[p].pair_tiles = b->tiles;
-        kp[p].pair_stride = b->pair_stride;
-        kp[p].pair_hdr = b->d_pair_hdr;
-        kp[p].pair_buf = b->d_pair_buf;
-        const char* t = getenv("FITOCT_TEST_PAIR_ABSENT");
-        kp[p].pair_test_absent = (t && atoi(t) != 0) ? 1 : 0;
-      }
+      // paired tiles: every problem's block names the batch's pairs
+      if (b->pairs.on()) b->pairs.apply(kp[p]);
     }
-    if (b->d_pair_hdr)
-      HIP_TRY(hipMemsetAsync(b->d_pair_hdr, 0, sizeof(int) * PAIR_HDR_INTS * (size_t)b->tiles, st));
+    if (b->pairs.on()) {
+      const int rc = b->pairs.zero(st);
+      if (rc) return rc;
+    }
     HIP_TRY(hipMemcpyAsync(b->d_kp, kp.data(), sizeof(KParams) * P, hipMemcpyHostToDevice, st));
     const fitoct_plan* p0 = b->plans[0];
     HIP_TRY(hipEventRecord(b->ev0, st));
-    HIP_TRY(launch(false, p0->mixed, p0->bpt, p0->nnp, kp[0], b->d_kp,
-                   b->d_pair_hdr ? pair_grid(b->tiles) : b->tiles, st, b->d_map));
+    HIP_TRY(launch(false, p0->mixed, p0->bpt, p0->nnp, kp[0], b->d_kp, b->grid(), st, b->d_map));
     HIP_TRY(hipEventRecord(b->ev1, st));
     HIP_TRY(hipEventSynchronize(b->ev1));
     float ms = 0.f;

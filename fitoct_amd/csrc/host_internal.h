@@ -27,6 +27,12 @@ double lp_constant(const fitoct_problem* p);
 int chain_outcome(int C, int D, const int* status, double* stepsize, double* inv_metric,
                   double* last_q);
 
+// Diagnostic stamps of a profiling build (stamps_report.cpp).  Launch-time environment
+// reads: whether FITOCT_STAMPS asks for them, and (bench_sweeps may be NULL)
+// FITOCT_BENCH_SWEEPS; the report of a host copy h[tiles][NSTAMP] on stderr.
+bool stamps_requested(int* bench_sweeps);
+void report_stamps(const long long* h, int tiles, bool bidi);
+
 // Every extern "C" entry that can allocate runs its body through guarded(): no C++
 // exception crosses the ABI (include/fitoct.h); a failure becomes a status + message.
 template <class F>

@@ -21,6 +21,46 @@ constexpr int MPW = 32;           // model-parameter words per chain (theta[3], 
 constexpr int POOL_VECS = 2;      // vectors per proposal-pool slot in HBM (q, grad)
 constexpr int KMAX = 24;          // max GP control points (K^-1 tile in LDS)
 constexpr int NSTAMP = 108;        // diagnostic stamps per tile (FITOCT_STAMPS)
+// Layout of a tile's NSTAMP stamps: written by the profiling build's kernels
+// (nuts_device.hip, kProfile), read by the report (stamps_report.cpp).  Cycles are
+// s_memtime, "rt" the 100 MHz s_memrealtime; a range's length is in brackets.
+enum StampSlot : int {
+  SS_SWEEPS = 0,          // sweeps of the tile (gradient wave 0)
+  SS_GRAD_BUSY = 1,       // gradient wave 0: cycles in sweeps
+  SS_NUTS_BUSY = 2,       // chain 0's NUTS wave: cycles outside its waits
+  SS_WALL = 3,            // gradient wave 0: cycles from start to end
+  SS_ACT_CYCLES = 4,      // [18] chain 0: cycles per action
+  SS_ACT_CALLS = 22,      // [18] ... and runs per action
+  SS_WAIT = 40,           // chain 0: cycles waiting for its gradient
+  SS_ROUNDS = 41,         // chain 0: NUTS rounds
+  SS_ENQ_TO_SWEPT = 42,   // of SS_WAIT: enqueue -> sweep done
+  SS_SWEPT_TO_RESUMED = 43,   // ... sweep done -> resumed
+  SS_FIRST_START = 44,    // enqueue -> first gradient wave starts
+  SS_LAST_START = 45,     // enqueue -> last gradient wave starts
+  SS_SUB = 48,            // [8] chain 0: cycles of sub-actions 0..7 (Chain::sub)
+  SS_WAVE_BUSY = 56,      // [8] cycles in sweeps by gradient wave
+  SS_RT_BEGIN = 64,       // rt at the tile's start
+  SS_RT_END = 65,         // rt at its end
+  SS_RT_FIRST_DONE = 66,  // rt when its first chain finished (0: none)
+  SS_CHAINS_DONE = 67,    // chains finished in this tile
+  SS_SUB_HI = 68,         // [4] sub-actions 8..11
+  SS_OCC_TIME = 72,       // [GMAX + 1] rt spent hosting k live chains
+  SS_OCC_SWEEPS = 77,     // [GMAX + 1] sweeps started while hosting k live chains
+  SS_BOOK_BUSY = 84,      // two-ended, the booking wave: cycles booking
+  SS_BOOK_WAIT = 85,      // ... waiting for its record
+  SS_BOOK_LEAVES = 86,    // ... leaves booked
+  SS_BOOK_IDLE = 87,      // ... idle between trees (reported; no kernel writes it now)
+  SS_PRODUCER = 88,       // [2 ends][4] producer: sweep wait, slot wait, leaves, in trees
+  SS_HELPER = 96,         // [2: primary, partner tile][2] booking helper: cycles, leaves
+  SS_PRODUCER_LEAF = 100, // [2 ends][4] producer: finish_grad, stage, hand-over, prior_part
+  SS_END = 108,
+};
+static_assert(SS_PRODUCER_LEAF + 2 * 4 == SS_END && SS_END <= NSTAMP, "stamp slots exceed NSTAMP");
+static_assert(SS_OCC_TIME + GMAX + 1 == SS_OCC_SWEEPS && SS_OCC_SWEEPS + GMAX + 1 <= SS_BOOK_BUSY,
+              "occupancy ranges overlap");
+// chain 0's LDS accumulators (ChainScalars::prof[0]): per action below PROF_SUB, then the
+// sub-actions' cycles
+constexpr int PROF_SUB = 20;
 constexpr int PAIR_HDR_INTS = 64; // paired tiles: hand-off words per pair (nuts_device.hip PairHdr)
 constexpr int PAIR_START_DOUBLES = 8;   // ... and per pair in pair_buf: the start's 4 vectors, then
                                         // these scalars, then the ring
@@ -98,7 +138,7 @@ struct KParams {
   double* fin_q;            // [chains][D]
   int* chain_status;        // [chains]
   long long* leapfrogs;     // [chains]
-  long long* stamps;        // optional [tiles][4]: half-steps, gradient busy, NUTS busy, total cycles
+  long long* stamps;        // optional [tiles][NSTAMP] diagnostic stamps (see StampSlot)
   int bench_sweeps;         // profiling build only (FITOCT_BENCH_SWEEPS): after the first
                             // position, each chain re-enqueues it this many times and stops
                             // (the sweep alone, no sampler work between sweeps)

@@ -29,13 +29,6 @@
 #include "host_internal.h"
 #include "plan_internal.h"
 
-#define HIP_TRY(expr)                                                                 \
-  do {                                                                                \
-    hipError_t e_ = (expr);                                                           \
-    if (e_ != hipSuccess)                                                             \
-      return fail(FITOCT_E_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-  } while (0)
-
 namespace fitoct {
 
 void block_range(int total, int n, int r, int& off, int& cnt) {
@@ -223,7 +216,7 @@ int group_plan_create(const fitoct_problem* prob, const fitoct_config* cfg,
   pl->kp.chain_offset = cfg->chain_offset;
   for (const fitoct_plan* sh : pl->shards) {
     pl->draws_bytes += sh->draws_bytes;
-    pl->tiles += sh->tiles;
+    pl->sched.tiles += sh->sched.tiles;
   }
   *out = guard.release();
   return FITOCT_OK;
@@ -233,7 +226,7 @@ int group_plan_info(const fitoct_plan* pl, fitoct_plan_info* info) {
   const int rc = fitoct_plan_get_info(pl->shards[0], info);
   if (rc) return rc;
   info->chains = pl->kp.chains;
-  info->tiles = pl->tiles;
+  info->tiles = pl->sched.tiles;
   info->draws_bytes = (int64_t)pl->draws_bytes;
   info->n_devices = (int32_t)pl->shards.size();
   return FITOCT_OK;

@@ -1532,12 +1532,12 @@ struct Chain {
 
   __device__ __forceinline__ int uni(int x) const { return __builtin_amdgcn_readfirstlane(x); }
   // diagnostic sub-action stamps (profiling build + FITOCT_STAMPS): cycles since t
-  // into prof[0][20 + i]
+  // into prof[0][PROF_SUB + i]
   __device__ __forceinline__ void sub(int i, long long& t) const {
     if (kProfile && Pr().stamps) {
       wave_fence();
       const long long n = (long long)__builtin_amdgcn_s_memtime();
-      if (lane == 0) Sp->prof[0][20 + i] += n - t;
+      if (lane == 0) Sp->prof[0][PROF_SUB + i] += n - t;
       t = n;
     }
   }
@@ -3233,8 +3233,8 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
       occ_t[min(max(lds_load(&live_chains), 0), GMAX)] +=
           (long long)__builtin_amdgcn_s_memrealtime() - occ_last;
       for (int k = 0; k <= GMAX; ++k) {
-        o[72 + k] = occ_t[k];
-        o[77 + k] = occ_n[k];
+        o[SS_OCC_TIME + k] = occ_t[k];
+        o[SS_OCC_SWEEPS + k] = occ_n[k];
       }
     }
   } else {           // ------------------------- NUTS waves
@@ -3528,12 +3528,12 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
       }
       if (helped && lane == 0) __atomic_store_n(&help_req[s], -1, __ATOMIC_RELAXED);   // its helper may leave
       if (kProfile && P.stamps != nullptr && lane == 0) {   // this end's producer (either tile)
-        AS_GLB long long* o = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP + 88 + 4 * s;
+        AS_GLB long long* o = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP + SS_PRODUCER + 4 * s;
         o[0] = pf_sw;
         o[1] = pf_may;
         o[2] = pf_n;
         o[3] = pf_tree;
-        AS_GLB long long* o2 = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP + 100 + 4 * s;
+        AS_GLB long long* o2 = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP + SS_PRODUCER_LEAF + 4 * s;
         o2[0] = pf_fg;
         o2[1] = pf_st;
         o2[2] = pf_ho;
@@ -3855,7 +3855,7 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
           }
         }
         if (kProfile && P.stamps != nullptr && lane == 0) {   // this tile's booking helper
-          AS_GLB long long* o = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP + 96 + 2 * role;
+          AS_GLB long long* o = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP + SS_HELPER + 2 * role;
           o[0] = pf_busy;
           o[1] = pf_n;
         }
@@ -4067,9 +4067,9 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
           if (bidi) {   // release the producers; they drain their sweeps
             if (kProfile && P.stamps != nullptr && lane == 0) {   // the booking's time
               AS_GLB long long* o = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP;
-              o[84] = ch.pf_busy;
-              o[85] = ch.pf_wait;
-              o[86] = ch.pf_n;
+              o[SS_BOOK_BUSY] = ch.pf_busy;
+              o[SS_BOOK_WAIT] = ch.pf_wait;
+              o[SS_BOOK_LEAVES] = ch.pf_n;
             }
             if (lane == 0) __atomic_store_n(&bd[BD_GEN], -1, __ATOMIC_RELAXED);
             Patience w;
@@ -4125,31 +4125,31 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
       if (lane == 0) atomicSub(&n_active, 1);
     }
   }
-  if (wstamp) ((AS_GLB long long*)P.stamps)[(size_t)tix * NSTAMP + 56 + wave] = t_wbusy;
+  if (wstamp) ((AS_GLB long long*)P.stamps)[(size_t)tix * NSTAMP + SS_WAVE_BUSY + wave] = t_wbusy;
   if (stamp) {
     AS_GLB long long* o = (AS_GLB long long*)P.stamps + (size_t)tix * NSTAMP;
     if (wave == 0) {
-      o[0] = n_items;
-      o[1] = t_busy;
-      o[3] = (long long)__builtin_amdgcn_s_memtime() - t_begin;
-      o[64] = rt_begin;
-      o[65] = (long long)__builtin_amdgcn_s_memrealtime();
-      o[66] = first_done_rt;
-      o[67] = chains_done_here;
+      o[SS_SWEEPS] = n_items;
+      o[SS_GRAD_BUSY] = t_busy;
+      o[SS_WALL] = (long long)__builtin_amdgcn_s_memtime() - t_begin;
+      o[SS_RT_BEGIN] = rt_begin;
+      o[SS_RT_END] = (long long)__builtin_amdgcn_s_memrealtime();
+      o[SS_RT_FIRST_DONE] = first_done_rt;
+      o[SS_CHAINS_DONE] = chains_done_here;
     } else {
-      o[2] = t_busy;
-      o[40] = t_wait;
-      o[42] = t_sweep;
-      o[43] = t_notice;
-      o[44] = t_st0;
-      o[45] = t_st1;
-      o[41] = n_items;
+      o[SS_NUTS_BUSY] = t_busy;
+      o[SS_WAIT] = t_wait;
+      o[SS_ENQ_TO_SWEPT] = t_sweep;
+      o[SS_SWEPT_TO_RESUMED] = t_notice;
+      o[SS_FIRST_START] = t_st0;
+      o[SS_LAST_START] = t_st1;
+      o[SS_ROUNDS] = n_items;
       for (int k = 0; k < 18; ++k) {
-        o[4 + k] = L.cs(0).prof[0][k];
-        o[22 + k] = L.cs(0).prof[1][k];
+        o[SS_ACT_CYCLES + k] = L.cs(0).prof[0][k];
+        o[SS_ACT_CALLS + k] = L.cs(0).prof[1][k];
       }
-      for (int k = 0; k < 8; ++k) o[48 + k] = L.cs(0).prof[0][20 + k];
-      for (int k = 0; k < 4; ++k) o[68 + k] = L.cs(0).prof[0][28 + k];
+      for (int k = 0; k < 8; ++k) o[SS_SUB + k] = L.cs(0).prof[0][PROF_SUB + k];
+      for (int k = 0; k < 4; ++k) o[SS_SUB_HI + k] = L.cs(0).prof[0][PROF_SUB + 8 + k];
     }
   }
 }

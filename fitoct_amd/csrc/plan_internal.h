@@ -10,12 +10,39 @@
 #include "fitoct.h"
 #include "host_internal.h"
 #include "kernel_params.h"
+#include "schedule.h"
+
+// a failed HIP call ends the enclosing function with FITOCT_E_HIP and its message
+#define HIP_TRY(expr)                                                                 \
+  do {                                                                                \
+    hipError_t e_ = (expr);                                                           \
+    if (e_ != hipSuccess)                                                             \
+      return fitoct::fail(FITOCT_E_HIP,                                               \
+                          std::string(#expr) + ": " + hipGetErrorString(e_));         \
+  } while (0)
+
+namespace fitoct {
+// Paired tiles (KParams::pair_*): the pairs' hand-off words and buffers of one launch,
+// owned by the plan or, over every problem's tiles, by the batch (fitoct_api.cpp)
+struct PairBuffers {
+  int* hdr = nullptr;      // [tiles][PAIR_HDR_INTS] hand-off words, zeroed per launch
+  double* buf = nullptr;   // [tiles][stride] starts and subtree records
+  int tiles = 0, stride = 0, test_absent = 0;
+  bool on() const { return hdr != nullptr; }
+  int alloc(int tiles, int ppl, const Switches& sw);
+  void apply(KParams& k) const;      // every pair_* field of a launch's parameter block
+  int zero(hipStream_t st) const;    // every word the pairs poll: before every launch
+  void free();
+};
+}  // namespace fitoct
 
 struct fitoct_plan {
   fitoct_problem prob{};
   fitoct_config cfg{};
   fitoct::KParams kp{};
-  int tiles = 0, bpt = 0, nnp = 15, ppl = 1, lds = 0, ncu = 0;
+  fitoct::Switches sw{};     // the planner's environment switches at fitoct_plan_create
+  fitoct::Schedule sched{};  // the launch schedule (schedule.cpp); a multi-device plan: tiles only
+  int bpt = 0, nnp = 15, ppl = 1, ncu = 0;
   bool mixed = false;
   int* d_mig = nullptr;       // chain-migration control block (see MigCtrl)
   double* d_mig_img = nullptr;
@@ -37,10 +64,7 @@ struct fitoct_plan {
   int* h_prog = nullptr;      // host-pinned [chains]: transitions done (kernel-written)
   int* h_cancel = nullptr;    // host-pinned flag polled by the kernel
   long long* d_stamps = nullptr;   // diagnostic stamps of the launch in flight
-  int* d_pair_hdr = nullptr;       // paired tiles (KParams::pair): hand-off words
-  double* d_pair_buf = nullptr;    // ... starts and rings
-  // blocks of the launch: the tiles, or with paired tiles a primary and a partner each
-  int grid() const { return kp.pair ? fitoct::pair_grid(tiles) : tiles; }
+  fitoct::PairBuffers pairs;       // paired tiles (sched.pair)
 
   // ---- multi-device plan (cfg.n_devices > 1; multi_device.cpp) ----
   // One single-device plan per device; shard r runs this plan's chains
@@ -70,9 +94,10 @@ struct fitoct_batch {
   // multi-device layer when another device's chain failed; cleared by each run
   int* h_cancel = nullptr;
   int* d_cancel = nullptr;    // its device alias
-  int* d_pair_hdr = nullptr;  // paired tiles (every problem's KParams::pair_*)
-  double* d_pair_buf = nullptr;
-  int pair_stride = 0;
+  fitoct::Switches sw{};      // the planner's environment switches at fitoct_batch_create
+  fitoct::PairBuffers pairs;  // paired tiles over the whole batch (every problem's KParams::pair_*)
+  // blocks of the launch: the tiles, or with paired tiles a primary and a partner each
+  int grid() const { return pairs.on() ? fitoct::pair_grid(tiles) : tiles; }
 
   // ---- multi-device batch: problems [sub_off[r], sub_off[r] + subs[r]->plans.size())
   // on sub-batch r, one device each (multi_device.cpp) ----

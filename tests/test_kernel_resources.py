@@ -12,9 +12,10 @@ or older than the kernel source, the family is recompiled device-only for the re
 
 Template arguments of ``nuts_kernel``: <R, BPT (bins per lane), NNP, PPL, MODE, FAM,
 MIG (chain migration), SPEC (speculative leaves), PAIR (paired tiles)>; the plan picks them
-in ``fitoct_api.cpp`` (tiles of one chain -> MIG = false, SPEC = true, and PAIR = true when
-twice the tiles fit on the chip; 1024 chains on 256 CUs -> G = 4, migration + tail
-speculation; batch mode -> MIG = false, SPEC = false).
+in ``csrc/schedule.cpp`` (``choose_schedule``: tiles of one chain -> MIG = false, SPEC = true,
+and PAIR = true when twice the tiles fit on the chip; 1024 chains on 256 CUs -> G = 4,
+migration + tail speculation; batch mode -> MIG = false, SPEC = false).
+``tests/test_schedule.py`` checks that the planner picks the instantiations listed below.
 """
 import os
 import subprocess
