@@ -329,14 +329,18 @@ __device__ __forceinline__ double swap16_add(double a, double b) {
   const double b2 = __builtin_bit_cast(double, ((uint64_t)hi[1] << 32) | lo[1]);
   return a2 + b2;
 }
-// same across the two 32-lane halves
-__device__ __forceinline__ double swap32_add(double a, double b) {
+// same across the two 32-lane halves; b2: the swapped b, dead after the sum
+__device__ __forceinline__ double swap32_add(double a, double b, double& b2) {
   const uint64_t ua = __builtin_bit_cast(uint64_t, a), ub = __builtin_bit_cast(uint64_t, b);
   const auto lo = __builtin_amdgcn_permlane32_swap((uint32_t)ua, (uint32_t)ub, false, false);
   const auto hi = __builtin_amdgcn_permlane32_swap((uint32_t)(ua >> 32), (uint32_t)(ub >> 32), false, false);
   const double a2 = __builtin_bit_cast(double, ((uint64_t)hi[0] << 32) | lo[0]);
-  const double b2 = __builtin_bit_cast(double, ((uint64_t)hi[1] << 32) | lo[1]);
+  b2 = __builtin_bit_cast(double, ((uint64_t)hi[1] << 32) | lo[1]);
   return a2 + b2;
+}
+__device__ __forceinline__ double swap32_add(double a, double b) {
+  double b2;
+  return swap32_add(a, b, b2);
 }
 
 // butterfly sum over the wave; every lane ends with the bitwise-identical value
@@ -774,21 +778,28 @@ __device__ __forceinline__ bool transpose_all_positive8(double (&v)[8], int lane
 }
 
 // The transposed butterfly for any NV <= 32 values: halves the live values per
-// step (ceil), a missing partner counts as zero.  Returns the lane's total and,
-// in idx, which value it is (-1: a padding lane).
+// step (ceil).  Returns the lane's total and, in idx, which value it is (-1: a
+// padding lane).
+// A value without a partner at a step belongs to the step's lower lanes alone: its
+// slot in the upper lanes is padding.  A padding slot is only ever sent to, and
+// summed in, padding slots (a lane receives the slot it keeps, whose index is the
+// sender's), and padding lanes store nothing (idx = -1), so what a padding slot
+// holds never reaches a result.  Such a value therefore needs no select and no
+// zero partner: every lane adds its partner's copy to its own, which in the lower
+// lanes is the same keep + received, same operands, same order, as with the
+// selects (each 4 v_cndmask per step), and in the upper lanes a sum nobody reads.
+// No x + 0.0 is formed in a lane that holds a value (before and after this form).
 template <int H, int N, int CTRL, int NV>
 __device__ __forceinline__ void tr_dpp_n(double (&v)[NV], bool up) {
 #pragma unroll
   for (int i = 0; i < H; ++i) {
-    double send, keep;
     if (i + H < N) {
-      send = up ? v[i] : v[i + H];
-      keep = up ? v[i + H] : v[i];
+      const double send = up ? v[i] : v[i + H];
+      const double keep = up ? v[i + H] : v[i];
+      v[i] = keep + dpp<CTRL>(send);
     } else {
-      send = up ? v[i] : 0.0;
-      keep = up ? 0.0 : v[i];
+      v[i] = v[i] + dpp<CTRL>(v[i]);
     }
-    v[i] = keep + dpp<CTRL>(send);
   }
 }
 template <int NV>
@@ -796,8 +807,15 @@ __device__ __forceinline__ double transpose_reduce(double (&v)[NV], int lane, in
   constexpr int c1 = (NV + 1) / 2, c2 = (c1 + 1) / 2, c3 = (c2 + 1) / 2, c4 = (c3 + 1) / 2;
   constexpr int c5 = (c4 + 1) / 2;
   static_assert(NV <= 32 && c5 == 1, "transpose_reduce: at most 32 values");
+  // (odd NV: the last value's swap partner is the first pair's swapped operand, dead after
+  // its sum, instead of a zero moved into a register pair for it: the lower half gets
+  // a_low + a_high as before, the upper half is a padding slot)
+  double spare = 0.0;
 #pragma unroll
-  for (int i = 0; i < c1; ++i) v[i] = swap32_add(v[i], i + c1 < NV ? v[i + c1] : 0.0);
+  for (int i = 0; i < c1; ++i) {
+    if (i == 0 && c1 < NV) v[i] = swap32_add(v[i], v[i + c1], spare);
+    else v[i] = swap32_add(v[i], i + c1 < NV ? v[i + c1] : spare);
+  }
 #pragma unroll
   for (int i = 0; i < c2; ++i) v[i] = swap16_add(v[i], i + c2 < c1 ? v[i + c2] : 0.0);
   tr_dpp_n<c3, c2, DPP_MIRROR>(v, (lane & 8) != 0);
@@ -855,15 +873,61 @@ struct Bins {
   }
 };
 
+// What parameter k's lane needs on every leaf but which depends only on (k, D, Nn, family):
+// fixed for the launch, so one NUTS wave writes it to LDS at start-up (load_kinv, before the
+// tile's first barrier; read only after it) and the leaf path reads it back (a ds_read is no
+// VALU issue) instead of re-deriving it from comparison chains.  Only a role, byte offsets
+// and constant coefficients: every value they select between is still computed per leaf.
+struct LaneRole {
+  double aw;   // horseshoe: weight of the lane's likelihood coefficient (prior_part)
+  double cc;   // horseshoe: the inverse-gamma shape of an r2 lane, 1/2 (global) or nu/2
+  int soff;    // byte offset of the bin sum the lane's gradient needs (finish_grad)
+  int aoff;    // horseshoe: byte offset in AUX of the scale / yGP its coefficient takes
+  int kind;    // horseshoe: RK_Z (a z_j lane), RK_R1 (an r1 lane), RK_R2 (the rest)
+  int pad;
+};
+enum RoleKind : int { RK_Z = 0, RK_R1 = 1, RK_R2 = 2 };
+static_assert(sizeof(LaneRole) == 32, "LaneRole: 32 B per lane");
+
+template <int FAM>
+__device__ __forceinline__ LaneRole lane_role(int k, int D, int Nn, double nu) {
+  LaneRole r;
+  // which bin sum lane k's gradient needs.  Past D (padded lanes) it is not used:
+  // finish_grad forms a gradient only under k < D.
+  int si = 0;
+  if (k < 3) si = 1 + k;
+  else if (k == D - 1) si = 0;
+  else if (k < 3 + Nn) si = 4 + (k - 3);
+  else if (FAM == FAM_HORSESHOE && k >= 5 + Nn && k < D) {
+    // local scale j of r1 (k = 5 + Nn + j) or r2 (k = 5 + 2 Nn + j)
+    const int x = k - 5 - Nn;
+    si = 4 + (x < Nn ? x : x - Nn);
+  }
+  r.soff = si * 8;
+  // the horseshoe's lanes 3 <= k < D - 1 (prior_part), in the forms prior_part used per leaf
+  const bool tz = k < 3 + Nn;
+  const bool r1l = k >= 5 + Nn && k < 5 + 2 * Nn, r2l = k >= 5 + 2 * Nn;
+  const bool tr1 = k == 3 + Nn || r1l;
+  r.cc = (k == 4 + Nn) ? 0.5 : 0.5 * nu;
+  const int ai = tz ? 32 + (k - 3) : r1l ? k - 5 - Nn : r2l ? k - 5 - 2 * Nn : 0;
+  r.aw = (tz || r1l) ? 1.0 : r2l ? 0.5 : 0.0;
+  r.aoff = (ai >= 0 && ai < NAUX ? ai : 0) * 8;   // (other lanes never read it: kept inside AUX)
+  r.kind = tz ? RK_Z : tr1 ? RK_R1 : RK_R2;
+  r.pad = 0;
+  return r;
+}
+
 // LDS carve -----------------------------------------------------------------
-// [ K^-1 (KMAX x KMAX, row stride NNP) | b (KMAX) | MP[GMAX][MPW] | PART[G][NGW][NSLOT] |
+// [ K^-1 (KMAX x KMAX, row stride NNP) | b (KMAX) | LaneRole[VLEN] | MP[GMAX][MPW] |
+//   PART[G][NGW][NSLOT] |
 //   G x chain{ ChainScalars | NVEC vectors | SUMS[NSLOT] | AUX[NAUX] | levels[max_depth][NLVL] } ]
 template <int PPL>
 struct Lds {
   static constexpr int VLEN = WAVE * PPL;
   static constexpr int KBYTES = (KMAX * KMAX + KMAX) * 8;
+  static constexpr int RBYTES = VLEN * (int)sizeof(LaneRole);   // the lane-role block, after b
   static __host__ __device__ constexpr int head_bytes(int G) {
-    return KBYTES + (GMAX * MPW + NGW * G * NSLOT) * 8;
+    return KBYTES + RBYTES + (GMAX * MPW + NGW * G * NSLOT) * 8;
   }
   static __host__ __device__ constexpr int chain_bytes(int max_depth) {
     // ... | levels[max_depth][NLVL][VLEN] | merge-uniform rings[max_depth][WAVE]
@@ -890,8 +954,13 @@ struct Lds {
   int G, cb;
   __device__ AS_LDS double* kinv() const { return (AS_LDS double*)base; }
   __device__ AS_LDS double* bv() const { return (AS_LDS double*)base + KMAX * KMAX; }
-  __device__ AS_LDS double* mp(int c) const { return (AS_LDS double*)(base + KBYTES) + c * MPW; }
-  __device__ AS_LDS double* part() const { return (AS_LDS double*)(base + KBYTES) + GMAX * MPW; }
+  __device__ AS_LDS LaneRole* lane_roles() const { return (AS_LDS LaneRole*)(base + KBYTES); }
+  __device__ AS_LDS double* mp(int c) const {
+    return (AS_LDS double*)(base + KBYTES + RBYTES) + c * MPW;
+  }
+  __device__ AS_LDS double* part() const {
+    return (AS_LDS double*)(base + KBYTES + RBYTES) + GMAX * MPW;
+  }
   __device__ AS_LDS char* chain(int c) const { return base + head_bytes(G) + c * cb; }
   __device__ AS_LDS ChainScalars& cs(int c) const { return *(AS_LDS ChainScalars*)chain(c); }
   __device__ AS_LDS double* vecs(int c) const {
@@ -1220,6 +1289,10 @@ struct Chain {
     return transpose_all_positive8(x, lane);
   }
   __device__ __forceinline__ bool is_log(int k) const { return k < 3 || k >= 3 + Pr().Nn; }
+  // parameter k's lane-role record (the tile's block sits after b: a constant offset from Kinv)
+  __device__ __forceinline__ const AS_LDS LaneRole* role(int k) const {
+    return (const AS_LDS LaneRole*)((const AS_LDS char*)Kinv + Lds<PPL>::KBYTES) + k;
+  }
 
   // ---------------- the point handed to the gradient phase ------------------
   // Stages q, caches its constrained values (QE) and, per family, yGP and the
@@ -1306,21 +1379,21 @@ struct Chain {
   // sums arrive (lik_part):
   //   grad_k = PG_k + CA_k * S[sidx(k)] + CB_k * famsum,   lp = pr_lp - 0.5 S0 pr_is2
   // with S = the bin sums after finish_grad's transform and famsum = sum_j FW_j S[4+j].
-  __device__ __forceinline__ int sidx(int k) const {   // which bin sum lane k's gradient needs
+  // Which bin sum lane k's gradient needs: for the horseshoe, whose local scales make it a
+  // comparison chain, the byte offset in the lane's role record (LaneRole::soff); the other
+  // families' two comparisons stay in registers (the role read moved their kernels past the
+  // SGPR-spill ceilings of tests/test_kernel_resources.py).
+  __device__ __forceinline__ int sidx(int k) const {
     const int D = Pr().D, Nn = Pr().Nn;
     if (k < 3) return 1 + k;
     if (k == D - 1) return 0;
     if (k < 3 + Nn) return 4 + (k - 3);
-    if (FAM == FAM_HORSESHOE && k >= 5 + Nn) {
-      // local scale j of r1 (k = 5 + Nn + j) or r2 (k = 5 + 2 Nn + j): (k - 5 - Nn) mod Nn on
-      // [0, 2 Nn) without the integer division (~25 VALU instructions per leaf in finish_grad;
-      // x - Nn wraps to a large unsigned value where x < Nn).  Past D (padded lanes; the modulo gave
-      // some 4 + j there) the value is not used: finish_grad forms a gradient only under k < D.
-      if (k >= D) return 0;
-      const unsigned x = (unsigned)(k - 5 - Nn);
-      return 4 + (int)min(x, x - (unsigned)Nn);
-    }
     return 0;
+  }
+  __device__ __forceinline__ const AS_LDS double* sum_at(const AS_LDS double* S, int k,
+                                                         int soff) const {
+    if constexpr (FAM == FAM_HORSESHOE) return (const AS_LDS double*)((const AS_LDS char*)S + soff);
+    else return S + sidx(k);
   }
 
   __device__ void prior_part() const {
@@ -1362,7 +1435,9 @@ struct Chain {
       if (k < D) {
         const double qk = qs[k];
         if (k < 3) {
-          const double thk = (k == 0) ? th0 : (k == 1) ? th1 : th2;
+          // th0 / th1 / th2 by lane.  Horseshoe: the lane's own read of the same word, no
+          // selects (in the other families' kernels the read costs spilled SGPRs)
+          const double thk = FAM == FAM_HORSESHOE ? qe[k] : (k == 0) ? th0 : (k == 1) ? th1 : th2;
           const double sdk = (k == 0) ? Sd0 : (k == 1) ? Sd1 : Sd2t;
           gk = 1.0 - thk * sdk;
           if (mono) gk -= tr * thk;
@@ -1396,17 +1471,18 @@ struct Chain {
           //   r1 (g, l): grad 1 - e^2         lp -e^2/2 + q          (half-normal + log-Jacobian)
           //   r2 (g, l): grad c (1/e - 1)     lp -c (q + 1/e)        (InvGamma(c, c) + log-Jacobian,
           //                                                         c = 1/2 global, nu/2 local)
+          // (which of the three a lane is, its shape c and where its coefficient's scale
+          // sits in AUX: the lane's role record)
           const double ek = qe[k];
-          const bool tz = k < 3 + Nn;
-          const bool r1l = k >= 5 + Nn && k < 5 + 2 * Nn, r2l = k >= 5 + 2 * Nn;
-          const bool tr1 = k == 3 + Nn || r1l;
-          const double cc = (k == 4 + Nn) ? 0.5 : 0.5 * Pr().nu;
+          const AS_LDS LaneRole* ro = role(k);
+          const int kind = ro->kind;
+          const bool tz = kind == RK_Z, tr1 = kind == RK_R1;
+          const double cc = ro->cc;
           const double e2 = ek * ek, ie = frcp(ek);
           gk = tz ? -qk : tr1 ? 1.0 - e2 : cc * ie - cc;
           lpc += tz ? -0.5 * qk * qk : tr1 ? fma(-0.5, e2, qk) : -cc * (qk + ie);
-          const int ai = tz ? 32 + (k - 3) : r1l ? k - 5 - Nn : r2l ? k - 5 - 2 * Nn : 0;
-          const double aw = (tz || r1l) ? 1.0 : r2l ? 0.5 : 0.0;
-          ck = aw * gyf * AUX[ai];
+          const double aw = ro->aw;
+          ck = aw * gyf * *(const AS_LDS double*)((const AS_LDS char*)AUX + ro->aoff);
         }
       }
       pg.a[s] = gk;
@@ -1434,8 +1510,12 @@ struct Chain {
     const double fw = (FAM == FAM_HORSESHOE && lane < Nn) ? AUX[64 + lane] : 0.0;
     double famsum = 0.0, S0 = 0.0;
     double srow[PPL];   // basis rows (MODE_ROWS): the bin sum each lane's gradient needs
+    int soff[PPL];      // ... and its byte offset among the sums (the lane's role record)
 #pragma unroll
-    for (int s = 0; s < PPL; ++s) srow[s] = 0.0;
+    for (int s = 0; s < PPL; ++s) {
+      srow[s] = 0.0;
+      soff[s] = FAM == FAM_HORSESHOE ? role(idx(s))->soff : 0;
+    }
     if (lik && !poly) {
       // each lane sums the partials of the sums it needs itself, in the SUMS path's order
       // (bitwise the same values): no store / wait / read-back before the gradient
@@ -1447,7 +1527,8 @@ struct Chain {
         S0 += pw[w * NSLOT];
         if (FAM == FAM_HORSESHOE) v += pw[w * NSLOT + jv];
 #pragma unroll
-        for (int s = 0; s < PPL; ++s) srow[s] += pw[w * NSLOT + sidx(idx(s))];
+        for (int s = 0; s < PPL; ++s)
+          srow[s] += *sum_at(pw + w * NSLOT, idx(s), soff[s]);
       }
       if (FAM == FAM_HORSESHOE) famsum = wave_sum(lane < Nn ? fw * v : 0.0);
     } else if (lik) {
@@ -1484,7 +1565,7 @@ struct Chain {
       const int k = idx(s);
       double gk = pg.a[s];
       if (lik && k < D) {
-        gk = fma(ca.a[s], poly ? SUMS[sidx(k)] : srow[s], gk);
+        gk = fma(ca.a[s], poly ? *sum_at(SUMS, k, soff[s]) : srow[s], gk);
         if (FAM == FAM_HORSESHOE && (k == 3 + Nn || k == 4 + Nn))
           gk = fma(k == 3 + Nn ? 1.0 : 0.5, famsum, gk);
       }
@@ -2908,7 +2989,7 @@ struct Chain {
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
-template <int PPL, int NNP>
+template <int PPL, int NNP, int FAM>
 __device__ __forceinline__ void load_kinv(KPc& P, const Lds<PPL>& L, int tid) {
   if (P.mode == MODE_POLY) {  // zero-padded to NNP x NNP so the device loops are fixed-size
     const int Nn = P.Nn;
@@ -2917,6 +2998,22 @@ __device__ __forceinline__ void load_kinv(KPc& P, const Lds<PPL>& L, int tid) {
       L.kinv()[i] = (i < NNP * NNP && r < Nn && c < Nn) ? P.Kinv[r * Nn + c] : 0.0;
     }
     if (tid < NNP) L.bv()[tid] = (tid < Nn) ? P.bvec[tid] : 0.0;
+  }
+  // the lane-role block (read by the horseshoe's leaf path only): the first NUTS wave, once per tile
+  if (FAM == FAM_HORSESHOE && (tid >> 6) == NGW) {
+    const int lane = tid & (WAVE - 1);
+#pragma unroll
+    for (int s = 0; s < PPL; ++s) {
+      const int k = s * WAVE + lane;
+      const LaneRole r = lane_role<FAM>(k, P.D, P.Nn, P.nu);
+      AS_LDS LaneRole* o = L.lane_roles() + k;
+      o->aw = r.aw;
+      o->cc = r.cc;
+      o->soff = r.soff;
+      o->aoff = r.aoff;
+      o->kind = r.kind;
+      o->pad = 0;
+    }
   }
 }
 
@@ -3086,7 +3183,7 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
   AS_GLB double* const xb = paired ? (AS_GLB double*)P.pair_buf + (size_t)tix * P.pair_stride : nullptr;
   __shared__ int pair_on;
 
-  load_kinv<PPL, NNP>(P, L, tid);
+  load_kinv<PPL, NNP, FAM>(P, L, tid);
   if (tid == 0) {
     q_reserve = 0;
     n_active = nct;
@@ -4164,7 +4261,7 @@ __global__ void __launch_bounds__(TPB, 2) logp_kernel(const KParams* __restrict_
   const int c0 = blockIdx.x * P.G;
   const int nct = min(P.G, P.chains - c0);
   __shared__ int done[GMAX];
-  load_kinv<PPL, NNP>(P, L, tid);
+  load_kinv<PPL, NNP, FAM>(P, L, tid);
   if (tid < GMAX) done[tid] = tid >= nct;
   __syncthreads();
   const int c = wave - NGW;
