@@ -55,7 +55,6 @@ SOURCES = [
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")
-HEADERS = ["kernel_params.h", "philox.h", "host_internal.h", "plan_internal.h", "schedule.h"]
 # FITOCT_HIPFLAGS="-DX=1 ...": extra device-compile flags for A/B variant libraries
 # (built with --force, copied aside, loaded through FITOCT_LIB_PATH)
 EXTRA = os.environ.get("FITOCT_HIPFLAGS", "").split()
@@ -77,10 +76,10 @@ def _flags() -> str:
 
 
 def _newest_input() -> float:
-    paths = [os.path.join(CSRC, s) for _, s, _, _ in SOURCES]
-    paths += [os.path.join(CSRC, h) for h in HEADERS]
-    paths += [os.path.join(INCLUDE, "fitoct.h"), os.path.abspath(__file__)]
-    return max(os.path.getmtime(p) for p in paths)
+    """Newest mtime of anything the library is built from: every source with the headers
+    it includes (_newest_dep), the public header and this script."""
+    deps = [_newest_dep(os.path.join(CSRC, s)) for s in {s for _, s, _, _ in SOURCES}]
+    return max(deps + [os.path.getmtime(os.path.join(INCLUDE, "fitoct.h"))])
 
 
 def _newest_dep(src: str) -> float:

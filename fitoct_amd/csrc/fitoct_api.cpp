@@ -233,7 +233,7 @@ bool build_poly(const fitoct_problem* p, const std::vector<double>& B, int nnp,
 // MODE_POLY with bins in registers: on an arithmetic depth grid the bins
 // tid + b*GT of one lane have t = t_tid * R^b (t_i = exp(u_i dg / s2), u_i linear
 // in i), which lets the sweep form a lane's moments by Horner in R^l
-// (nuts_device.hip moments_geo).  Accepted only if every x_i lies on the line
+// (sweep_math.h moments_geo).  Accepted only if every x_i lies on the line
 // through x_0 and x_{N-1} to 1e-12 of the range and no (R^l)^b can overflow.
 bool geo_ratios(const fitoct_problem* p, int nnp, int bpt, double* R) {
   const int N = p->N, Nn = p->Nn;

@@ -61,7 +61,7 @@ static_assert(SS_OCC_TIME + GMAX + 1 == SS_OCC_SWEEPS && SS_OCC_SWEEPS + GMAX + 
 // chain 0's LDS accumulators (ChainScalars::prof[0]): per action below PROF_SUB, then the
 // sub-actions' cycles
 constexpr int PROF_SUB = 20;
-constexpr int PAIR_HDR_INTS = 64; // paired tiles: hand-off words per pair (nuts_device.hip PairHdr)
+constexpr int PAIR_HDR_INTS = 64; // paired tiles: hand-off words per pair (dev_global.h PairHdr)
 constexpr int PAIR_START_DOUBLES = 8;   // ... and per pair in pair_buf: the start's 4 vectors, then
                                         // these scalars, then the ring
 // the kernel's static LDS (rings, hand-off words, counters: 352 B measured, the

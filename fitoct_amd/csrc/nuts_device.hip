@@ -18,20 +18,8 @@
 //     order and count their completions per chain, the NUTS wave resumes when
 //     all 4 sweeps are in.  No barrier after start-up: each chain's sampler
 //     latency hides behind the sweeps of the tile's other chains.
-//   * gradient waves: the N depth bins are strided over 256 lanes; each lane
-//     keeps its bins' data resident in VGPRs for the whole run (read from HBM
-//     once per tile, shared by all G chains; up to 8 bins per lane, or 16 in
-//     the compact layout for arithmetic depth grids).  For the
-//     built-in uniform-grid SE basis (MODE_POLY) the GP basis factorises as
-//     K(x~_i, g_l) = a_i t_i^l b_l, so a bin needs 5 registers (c*x, y, 1/uy,
-//     t, a) instead of a 16-wide basis row: dL_i = a_i P(t_i) by Horner on the
-//     chain's coefficients c = b .* K^-1 yGP, and B^T h = K^-1 (b .* M) from
-//     the moments M_l = sum_i h_i a_i t_i^l.  A user-supplied basis keeps its
-//     rows in registers (MODE_ROWS, fp32) or streams them (MODE_STREAM).
-//     Per chain a lane accumulates 4+NNP partial sums; a transposed butterfly
-//     built from v_permlane32_swap / v_permlane16_swap / DPP row mirrors
-//     reduces them across the wave (no LDS round trips), and 4 per-wave
-//     partials land in LDS.
+//   * gradient waves: the likelihood sweep over the lanes' resident bins (sweep_math.h,
+//     gradient_pass.h).
 //   * NUTS phase (wave 4+c drives chain c): lane k holds parameter k.  The wave
 //     sums the 4 partials, completes lp / grad with the priors and the
 //     log-Jacobians, and advances the chain's state machine.  Stan's recursive
@@ -46,6 +34,15 @@
 //     two producers leapfrog the trajectory's backward and forward ends at once and a
 //     helper books the leaves in Stan's tree order ("Two-ended trajectories" below).
 //
+// The layers beneath the chain each have a header, included below in dependency order
+// (DESIGN.md §4 has the map): dev_common.h, dev_global.h, wave_math.h, sweep_math.h,
+// lds_layout.h, gradient_pass.h; each opens with a description of its layer.  The split is
+// not finished: the chain (struct Chain), migration's receiving side and the kernel are
+// still in this file and are to move, in that order and as they stand, to chain.h,
+// tile_migrate.h and nuts_kernel.h; the log-density kernel, the family's instantiations and
+// the launchers stay.  namespace fitoct opens in dev_common.h and closes at the end of
+// this file.
+//
 // Random numbers are addressable Philox draws (philox.h), identical to the CPU
 // oracle's, so short horizons of GPU and CPU chains coincide draw for draw.
 #include <hip/hip_runtime.h>
@@ -56,435 +53,9 @@
 #include "kernel_params.h"
 #include "philox.h"
 
-namespace fitoct {
-
-// Explicit address spaces: LDS (3), global (1), constant (4).  Generic pointers
-// would compile to FLAT instructions, which count in both vmcnt and lgkmcnt --
-// every LDS wait would then also wait for the sampler's outstanding HBM stores.
-#define AS_LDS __attribute__((address_space(3)))
-#define AS_GLB __attribute__((address_space(1)))
-#define AS_CST __attribute__((address_space(4)))
-using KPc = const AS_CST KParams;
-
-enum { FAM_NORMAL = 0, FAM_LASSO = 1, FAM_HORSESHOE = 2, FAM_MONO = 3 };
-// (round 6: the A/B switches measured "off" or "rejected" in DESIGN.md §4 are gone from
-// the kernel; what is left compiles to the measured defaults.  The only remaining build
-// switches are the ordering fallbacks FITOCT_LOCAL_FENCE / FITOCT_LDS_INORDER and the
-// profiling build FITOCT_PROFILE.)
-// 16 bins per lane (config 4): moments are formed per group of 8 bins
-constexpr int BPT16_GROUP = 8;
-
-// Cycle stamps (FITOCT_STAMPS) exist only in a profiling build
-// (FITOCT_PROFILE=1 python -m fitoct_amd.build): the production kernels carry
-// no per-action timing code at all.
-#ifndef FITOCT_PROFILE
-#define FITOCT_PROFILE 0
-#endif
-constexpr bool kProfile = FITOCT_PROFILE != 0;
-// -DFITOCT_ASM_MARKS: assembly comments at action boundaries, for per-action
-// instruction counts in a -S listing (scripts/asm_actions.py); no code otherwise
-#ifdef FITOCT_ASM_MARKS
-#define FITOCT_MARK(name) asm volatile(";MARK " #name)
-#else
-#define FITOCT_MARK(name)
-#endif
-enum { ERR_INIT = -4, ERR_NUMERIC = -5, ERR_TIMEOUT = -6, ERR_CANCELLED = -8 };
-
-// vectors kept in LDS per chain (lane-private elements)
-enum VecId : int {
-  V_CUR_Q, V_CUR_P, V_CUR_G,
-  V_E0_Q, V_E0_P, V_E0_G,      // backward end of the trajectory
-  V_E1_Q, V_E1_P, V_E1_G,      // forward end
-  V_SMP_Q, V_SMP_G,            // z_sample (its momentum enters only the energy: smp_h)
-  V_MINV, V_WF_M, V_WF_M2,     // metric + Welford
-  V_RHO, V_PNEAR,              // trajectory momentum sum, near end of old trajectory
-  V_QS, V_QE,                  // staged q and its constrained values (exp on positive params)
-  V_PG, V_CA,                  // prior part of grad, likelihood coefficient (prior_part)
-  NVEC
-};
-// U-turn record of one tree level (LDS)
-enum LvlId : int { K_PBEG = 0, K_PEND = 1, K_RHO = 2, NLVL = 3 };
-// proposal pool slot (HBM): q and g of a candidate sample.  Its momentum is dead once it is
-// a candidate (the next transition draws a fresh one) except in the energy__ diagnostic,
-// H(z_sample), which is the candidate leaf's own Hamiltonian h: kept as a scalar (pool_h)
-enum PoolId : int { P_Q = 0, P_G = 1, NPOOL = POOL_VECS };
-constexpr int NAUX = 96;   // per chain: yGP[32] | horseshoe lambda_j*tau [32] | FW_j [32]
-
-struct ChainScalars {
-  int state, t, depth, leaf, dir, n_leapfrog, divergent, init_attempt;
-  int da_counter, win_counter, win_size, win_next, wf_n, ss_trial, ss_dir, ss_window;
-  int status, win_on, init_buf, term_buf, pool_used, lsw_e, spec_we, pad2;
-  int st_prop[MAXDEPTH];
-  int st_w_e[MAXDEPTH];
-  double H0, lsw_m, sum_metro, eps, eps_used, mu, s_bar, x_bar, ss_H0, lf_e;
-  double cur_lp, cur_s2, smp_lp, smp_s2;
-  double pr_lp, pr_is2, u_top, spec_wm;   // spec_wm, spec_we, spec_h: the speculative
-                                          // path's booked leaf weight and energy
-  int u_blk[MAXDEPTH];     // which block of 64 merge uniforms each level's ring holds (-1: none)
-  double end_lp[2], end_s2[2];
-  double st_w_m[MAXDEPTH];
-  double pool_lp[MAXDEPTH + 1], pool_s2[MAXDEPTH + 1];
-  long long leapfrogs;
-  double spec_h;
-  // Hamiltonian -lp + K(p) of each pool candidate and of the sample (energy__)
-  double pool_h[MAXDEPTH + 1], smp_h;
-  // the running subtree's sum of the leaves' acceptance terms (added to sum_metro when the
-  // subtree ends, so two-ended trajectories can sum per subtree and stay bitwise equal)
-  double sub_metro, pad_sm;
-  long long prof[2][32];   // diagnostic build: cycles and calls per action
-};
-static_assert(sizeof(ChainScalars) % 16 == 0, "LDS carve alignment");
-
-// two-ended trajectories (P.bidi): the tile's hand-off words in LDS.  BD_GEN: the transition
-// (1..BD_GEN_MASK, -1: the chain has finished); BD_PROD + s: stream s's published leaves as
-// (gen << 16) | count; BD_CONS + s: leaves of stream s the helper has booked; BD_END: the
-// transition whose tree the helper has ended; BD_EXIT: producers that have left
-// TW_*: who grows the ends -- the producers' NUTS slots (TW_SLOT, TW_SLOT + 1; a tile of
-// one chain: 1, 2), the chain's slot and index (TW_CHAIN, TW_LC; written by bidi_begin);
-// migrating tiles recruit producers at run time (TW_CLAIM: role bits claimed, TW_JOIN:
-// producers in place; see receive_chain)
-enum BdWord : int {
-  BD_GEN = 0, BD_PROD = 1, BD_CONS = 3, BD_END = 5, BD_EXIT = 6,
-  TW_CLAIM = 7, TW_JOIN = 8, TW_SLOT = 9, TW_CHAIN = 11, TW_LC = 12, TW_BUSY = 13, BD_N = 16
-};
-constexpr int BD_GEN_MASK = (1 << 15) - 1;
-// BD_GEN | BD_ENDED: a migrating tile's chain has booked transition BD_GEN's tree to its end
-// (its producers stop, and wait for the next transition or the launch's end)
-constexpr int BD_ENDED = 1 << 20;
-// a producer runs at most this many doublings past the booked one (lookahead 1 / 2 / 5
-// measured -1.0 / -0.2 / +-0 % on config 2, profiles/r05_ab_stage.txt)
-constexpr int BIDI_LOOK = 3;
-
-constexpr long long SPIN_LIMIT = 1LL << 26;   // polls (~2 s) before a wait reads the clock
-constexpr unsigned long long TICKS_PER_S = 100000000ULL;   // s_memrealtime: 100 MHz
-// a wait for one leaf's work (a sweep, a booking, a producer's record): far above any real
-// leaf (microseconds; a deep tree's whole trajectory is bounded separately, MIG_WAIT_TICKS)
-constexpr unsigned long long LEAF_WAIT_TICKS = 30ULL * TICKS_PER_S;
-
-// The hang guard of every wait in the kernel.  The first SPIN_LIMIT polls read no clock;
-// past them the wait is bounded in REAL time (s_memrealtime), not in polls, so a slow
-// sweep, a profiler or a deep tree never fails a healthy chain with ERR_TIMEOUT, and a
-// fault still ends the launch.  expired(T) is true once T ticks passed since poll SPIN_LIMIT.
-struct Patience {
-  long long n = 0;
-  unsigned long long t0 = 0;
-  __device__ __forceinline__ bool expired(unsigned long long ticks) {
-    if (++n <= SPIN_LIMIT) return false;
-    const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-    if (n == SPIN_LIMIT + 1) t0 = t;
-    __builtin_amdgcn_s_sleep(32);
-    return t - t0 > ticks;
-  }
-};
-
-__device__ __forceinline__ void wave_fence() {
-  // orders this wave's LDS traffic: every earlier ds_* op has completed and the
-  // compiler may not move memory accesses across this point.
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-}
-// A wave reading back what its own lanes just stored to LDS: the DS operations of one
-// wave are performed in issue order (the AMDGPU memory model), so only the compiler must
-// keep the order -- no wait for the stores to complete (FITOCT_LOCAL_FENCE=0: the full wait)
-#ifndef FITOCT_LOCAL_FENCE
-#define FITOCT_LOCAL_FENCE 1
-#endif
-__device__ __forceinline__ void wave_order() {
-#if FITOCT_LOCAL_FENCE
-  asm volatile("" ::: "memory");
-#else
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-}
-// A wave publishing LDS data to another wave of the tile by a later LDS store or atomic (a
-// sweep's partial sums before grad_cnt, a position's MP before its ring entry, a leaf record
-// before its count): the LDS performs one wave's DS operations in issue order, so a reader
-// that sees the count and then reads the data sees the data.  FITOCT_LDS_INORDER=0: wait for
-// the data stores to complete first (s_waitcnt lgkmcnt(0)).
-#ifndef FITOCT_LDS_INORDER
-#define FITOCT_LDS_INORDER 1
-#endif
-__device__ __forceinline__ void wave_publish() {
-#if FITOCT_LDS_INORDER
-  asm volatile("" ::: "memory");
-#else
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-}
-
-// ---------------------------------------------------------------------------
-// chain migration between tiles: agent-scope atomics on global memory (the
-// tiles of a launch sit on different XCDs, each with its own L2; release /
-// acquire at agent scope write back / invalidate L2 as the gfx950 memory model
-// requires).  Rare operations (at most one per transition), so generic pointers.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ int g_load(AS_GLB int* p) {
-  return __hip_atomic_load((int*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int g_add(AS_GLB int* p, int v) {
-  return __hip_atomic_fetch_add((int*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int g_or(AS_GLB int* p, int v) {
-  return __hip_atomic_fetch_or((int*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int g_and(AS_GLB int* p, int v) {
-  return __hip_atomic_fetch_and((int*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// run-time progress / cancellation: host-pinned fine-grained memory, read by the
-// host while the kernel runs (system scope; at most one access per transition)
-__device__ __forceinline__ void sys_store(int* p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ int sys_load(const int* p) {
-  return __hip_atomic_load(const_cast<int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ bool g_cas(AS_GLB int* p, int expect, int v) {
-  return __hip_atomic_compare_exchange_strong((int*)p, &expect, v, __ATOMIC_RELAXED,
-                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-struct MigView {   // KParams::mig carved per MigCtrl
-  AS_GLB int* hdr;
-  AS_GLB int* load;
-  AS_GLB int* fmask;
-  AS_GLB int* mbox;
-  __device__ MigView(int* base, int tiles)
-      : hdr((AS_GLB int*)base), load((AS_GLB int*)base + MIG_HDR), fmask(load + tiles),
-        mbox(fmask + tiles) {}
-};
-constexpr unsigned long long MIG_WAIT_TICKS = 120ULL * TICKS_PER_S;
-
-// ---------------------------------------------------------------------------
-// paired tiles (KParams::pair): the forward end of a one-chain tile's two-ended trajectories
-// grows in a partner tile, with its own four gradient waves.  Everything crossing between
-// the two workgroups is a write-through (sc1) agent-scope store, drained by the storing wave
-// (s_waitcnt vmcnt(0)) before the one word that publishes it, and read with sc1 loads only
-// (relaxed agent-scope atomics: global_load / global_store ... sc1, no L1 copy on either
-// side), so no L2 write-back or invalidation is needed whichever XCDs the two tiles sit on.
-// Per pair: PAIR_HDR_INTS hand-off words (zeroed before every launch), then in pair_buf
-// the transition's start and one subtree record of the forward end.
-// ---------------------------------------------------------------------------
-enum PairHdr : int {
-  // primary -> partner: the transition (its start is in pair_buf; -1: the chain finished),
-  // the booking's records taken of the forward end and the booked depth, each (gen << 16) | v;
-  // the chain's index and the transition's number t
-  PH_GEN = 0, PH_CONS = 1, PH_DEPTH = 2, PH_LC = 3, PH_T = 4,
-  PH_COUNT = 32,   // partner -> primary: (gen << 16) | forward-end subtree records published
-  PH_STATE = 48    // PairState bits (both, atomics); PAIR_HDR_INTS words per pair (kernel_params.h)
-};
-// The pair's hand-shake: the primary marks START when it begins; the partner joins (START ->
-// START | JOIN) only if the primary has begun, else marks LOCAL and leaves; the primary decides
-// at its chain's first transition (START -> START | LOCAL unless the partner has joined).  So
-// a partner that is not resident (a busy GPU) never holds up its primary, and a primary only
-// ever waits for a partner that is running: the unpaired tile grows both ends itself.
-enum PairState : int { PS_START = 1, PS_JOIN = 2, PS_LOCAL = 4 };
-constexpr unsigned long long PAIR_JOIN_TICKS = 10000;   // 100 us (s_memrealtime: 100 MHz)
-__device__ __forceinline__ void x_st(AS_GLB double* p, double v) {
-  __hip_atomic_store((AS_GLB unsigned long long*)p, __builtin_bit_cast(unsigned long long, v),
-                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double x_ld(const AS_GLB double* p) {
-  return __builtin_bit_cast(double, __hip_atomic_load((AS_GLB unsigned long long*)p,
-                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ void x_sti(AS_GLB int* p, int v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ int x_ldi(AS_GLB int* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// every sc1 store of this wave has reached memory (before the word that publishes them)
-__device__ __forceinline__ void x_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// ---------------------------------------------------------------------------
-// cross-lane moves of doubles without LDS (DPP row ops, gfx950 permlane swaps)
-// ---------------------------------------------------------------------------
-constexpr int DPP_XOR1 = 0xB1;         // quad_perm(1,0,3,2)
-constexpr int DPP_XOR2 = 0x4E;         // quad_perm(2,3,0,1)
-constexpr int DPP_QREV = 0x1B;         // quad_perm(3,2,1,0): flip bits 0,1
-constexpr int DPP_HALF_MIRROR = 0x141; // lane i <-> 7-i within 8: flip bits 0..2
-constexpr int DPP_MIRROR = 0x140;      // lane i <-> 15-i within 16: flip bits 0..3
-
-// (bound_ctrl: a disabled source lane reads 0, as the zero 'old' operand of update_dpp
-// gave, without a v_mov of that zero before every DPP move)
-template <int CTRL>
-__device__ __forceinline__ double dpp(double x) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const int lo = __builtin_amdgcn_mov_dpp((int)(uint32_t)u, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_mov_dpp((int)(uint32_t)(u >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
-}
-// v_readlane of a double (lane index wave-uniform)
-__device__ __forceinline__ double rl(double x, int l) {
-  const uint64_t u = __builtin_bit_cast(uint64_t, x);
-  const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)u, l);
-  const uint32_t hi = __builtin_amdgcn_readlane((uint32_t)(u >> 32), l);
-  return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
-}
-// a' = a with rows {1,3} (lanes 16-31, 48-63) replaced by b's rows {0,2};
-// b' = b with rows {0,2} replaced by a's rows {1,3}.  Returns a' + b'.
-__device__ __forceinline__ double swap16_add(double a, double b) {
-  const uint64_t ua = __builtin_bit_cast(uint64_t, a), ub = __builtin_bit_cast(uint64_t, b);
-  const auto lo = __builtin_amdgcn_permlane16_swap((uint32_t)ua, (uint32_t)ub, false, false);
-  const auto hi = __builtin_amdgcn_permlane16_swap((uint32_t)(ua >> 32), (uint32_t)(ub >> 32), false, false);
-  const double a2 = __builtin_bit_cast(double, ((uint64_t)hi[0] << 32) | lo[0]);
-  const double b2 = __builtin_bit_cast(double, ((uint64_t)hi[1] << 32) | lo[1]);
-  return a2 + b2;
-}
-// same across the two 32-lane halves; b2: the swapped b, dead after the sum
-__device__ __forceinline__ double swap32_add(double a, double b, double& b2) {
-  const uint64_t ua = __builtin_bit_cast(uint64_t, a), ub = __builtin_bit_cast(uint64_t, b);
-  const auto lo = __builtin_amdgcn_permlane32_swap((uint32_t)ua, (uint32_t)ub, false, false);
-  const auto hi = __builtin_amdgcn_permlane32_swap((uint32_t)(ua >> 32), (uint32_t)(ub >> 32), false, false);
-  const double a2 = __builtin_bit_cast(double, ((uint64_t)hi[0] << 32) | lo[0]);
-  b2 = __builtin_bit_cast(double, ((uint64_t)hi[1] << 32) | lo[1]);
-  return a2 + b2;
-}
-__device__ __forceinline__ double swap32_add(double a, double b) {
-  double b2;
-  return swap32_add(a, b, b2);
-}
-
-// butterfly sum over the wave; every lane ends with the bitwise-identical value
-__device__ __forceinline__ double wave_sum(double x) {
-  x += dpp<DPP_XOR1>(x);
-  x += dpp<DPP_XOR2>(x);
-  x += dpp<DPP_HALF_MIRROR>(x);
-  x += dpp<DPP_MIRROR>(x);
-  x = swap16_add(x, x);
-  return swap32_add(x, x);
-}
-__device__ __forceinline__ void wave_sum2(double& a, double& b) {
-  a += dpp<DPP_XOR1>(a);
-  b += dpp<DPP_XOR1>(b);
-  a += dpp<DPP_XOR2>(a);
-  b += dpp<DPP_XOR2>(b);
-  a += dpp<DPP_HALF_MIRROR>(a);
-  b += dpp<DPP_HALF_MIRROR>(b);
-  a += dpp<DPP_MIRROR>(a);
-  b += dpp<DPP_MIRROR>(b);
-  a = swap16_add(a, a);
-  b = swap16_add(b, b);
-  a = swap32_add(a, a);
-  b = swap32_add(b, b);
-}
-
-// N independent butterfly sums, stage by stage (the DPP / permlane moves of the
-// N values overlap instead of serialising N reductions)
-template <int N>
-__device__ __forceinline__ void wave_sum_n(double (&x)[N]) {
-#pragma unroll
-  for (int i = 0; i < N; ++i) x[i] += dpp<DPP_XOR1>(x[i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) x[i] += dpp<DPP_XOR2>(x[i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) x[i] += dpp<DPP_HALF_MIRROR>(x[i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) x[i] += dpp<DPP_MIRROR>(x[i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) x[i] = swap16_add(x[i], x[i]);
-#pragma unroll
-  for (int i = 0; i < N; ++i) x[i] = swap32_add(x[i], x[i]);
-}
-
-// exp on the sampler side: reduction by ln2 (hi/lo), Taylor degree 12 on
-// |r| <= ln2/2, n = round(x log2 e) from the 1.5*2^52 shifter fed straight to
-// v_ldexp_f64 (<= 2 ulp from the library exp, scripts/micro/acc.hip; no special
-// cases: x is clamped to [-746, 710], where exp is 0 / inf either way).
-// v_fma_f64 with all three operands in VGPRs.  In the sampler's code the compiler keeps
-// fexp's coefficients in VGPRs (its SGPRs are spent) and forms p * r + c as a copy of c into
-// the destination plus a v_fmac_f64: two VALU instructions per Horner step.  Same operation.
-// Every sampler uses it (the migrating ones too since write_mp's single exp freed their
-// registers; round 3 had to leave them out: profiles/r03_ab_fmav.txt).  The addend in an SGPR
-// pair instead costs the migrating kernels 23-29 more spilled SGPRs for the same speed
-// (profiles/r07_ab_sampler_valu.txt).
-__device__ __forceinline__ double fma_v(double a, double b, double c) {
-  double d;
-  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-  return d;
-}
-__device__ __forceinline__ double fexp(double x) {
-  x = fmin(fmax(x, -746.0), 710.0);
-  const double SH = 6755399441055744.0;   // 1.5 * 2^52
-  const double t = fma(x, 1.4426950408889634, SH);
-  const double n = t - SH;
-  const int ni = (int)(uint32_t)__builtin_bit_cast(uint64_t, t);
-  double r = fma(-n, 6.93147180369123816490e-01, x);
-  r = fma(-n, 1.90821492927058770002e-10, r);
-  double p = 2.08767569878680989792e-09;   // 1/12!
-  p = fma_v(p, r, 2.50521083854417187751e-08);
-  p = fma_v(p, r, 2.75573192239858906526e-07);
-  p = fma_v(p, r, 2.75573192239858906526e-06);
-  p = fma_v(p, r, 2.48015873015873015873e-05);
-  p = fma_v(p, r, 1.98412698412698412698e-04);
-  p = fma_v(p, r, 1.38888888888888888889e-03);
-  p = fma_v(p, r, 8.33333333333333333333e-03);
-  p = fma_v(p, r, 4.16666666666666666667e-02);
-  p = fma_v(p, r, 1.66666666666666666667e-01);
-  p = fma_v(p, r, 0.5);
-  p = fma_v(p, r, 1.0);
-  p = fma_v(p, r, 1.0);
-  return ldexp(p, ni);
-}
-// 1/x to <= 1 ulp: v_rcp_f64 and one Newton step (x finite, nonzero)
-__device__ __forceinline__ double frcp(double x) {
-  const double r = __builtin_amdgcn_rcp(x);
-  return fma(r, fma(-x, r, 1.0), r);
-}
-
-// Multinomial trajectory weights exp(H0 - H) as extended-exponent floats
-// m * 2^e (m in [1/2, 1) or 0): the merges of base_nuts (log_sum_exp of log
-// weights, then u < exp(lsw_final - lsw_subtree)) become an add and a multiply,
-// with no exp / log1p per merge and no overflow for any energy change.  The
-// oracle (oracle/fitoct_oracle.c) uses the same representation.
-struct XF {
-  double m;
-  int e;
-};
-__device__ __forceinline__ XF xf_norm(double m, int e) {
-  int k;
-  const double f = frexp(m, &k);
-  return XF{f, f == 0.0 ? 0 : e + k};
-}
-__device__ __forceinline__ XF xf_exp(double x) {   // exp(x), x <= +inf; -inf -> 0
-  if (x > -700.0 && x < 700.0) return xf_norm(fexp(x), 0);
-  // above 1e8 (an energy drop no trajectory of a finite start reaches) the weight
-  // saturates: the exponent stays within int, and so does the exponent difference of
-  // two weights in xf_u_below (>= -1.45e9 - 1.45e8)
-  if (!(x < 1.0e8)) x = 1.0e8;
-  // below -1e9 (a divergent leaf: its weight is never merged) the exponent would not fit
-  // an int; the weight is 0 to every digit the merges can resolve
-  if (!(x > -1.0e9)) return XF{0.0, 0};
-  const double k = floor(x * 1.4426950408889634);   // log2(e)
-  return xf_norm(fexp(fma(-k, 0.6931471805599453, x)), (int)k);
-}
-__device__ __forceinline__ XF xf_add(XF a, XF b) {
-  if (a.m == 0.0) return b;
-  if (b.m == 0.0) return a;
-  const int e = a.e > b.e ? a.e : b.e;
-  return xf_norm(ldexp(a.m, a.e - e) + ldexp(b.m, b.e - e), e);
-}
-__device__ __forceinline__ bool xf_gt(XF a, XF b) {   // a > b (both >= 0)
-  if (a.m == 0.0) return false;
-  if (b.m == 0.0) return true;
-  return a.e != b.e ? a.e > b.e : a.m > b.m;
-}
-__device__ __forceinline__ bool xf_u_below(double u, XF a, XF b) {   // u < a / b
-  if (b.m == 0.0) return false;   // Stan: u < exp(-inf - -inf) = NaN is false
-  return ldexp(u * b.m, b.e - a.e) < a.m;
-}
-__device__ __forceinline__ double xf_val(XF a) { return ldexp(a.m, a.e); }
-
-
-__device__ __forceinline__ void normal_pair(RngKey k, uint32_t c0, uint32_t c1, uint32_t c2,
-                                            uint32_t c3, double& n0, double& n1) {
-  U4 c = {c0, c1, c2, c3};
-  U4 r = philox4x32_10(c, k.k0, k.k1);
-  const double u1 = u53(r.x, r.y), u2 = u53(r.z, r.w);
-  const double rad = sqrt(-2.0 * log(1.0 - u1));
-  double sn, cs;
-  sincospi(2.0 * u2, &sn, &cs);   // angle 2*pi*u2; sinpi/cospi need no Payne-Hanek reduction
-  n0 = rad * cs;
-  n1 = rad * sn;
-}
+#include "dev_common.h"
+#include "dev_global.h"
+#include "wave_math.h"
 
 // The sweep's arithmetic is contracted only where the source writes a * b + c as one
 // expression (or calls fma): HIP's default, fast contraction across statements, let the
@@ -494,609 +65,9 @@ __device__ __forceinline__ void normal_pair(RngKey k, uint32_t c0, uint32_t c1, 
 // as well costs config 5 7 %, scripts/gpu_r5_variants.sh); config 5 runs 1.7 % below the
 // fast contraction, config 3 0.5 % (profiles/r05_ab_contract.txt).
 #pragma clang fp contract(on)
-
-// ---------------------------------------------------------------------------
-// per-bin arithmetic (the likelihood sweep)
-// ---------------------------------------------------------------------------
-template <class R> __device__ __forceinline__ R rcp_(R x);
-template <> __device__ __forceinline__ double rcp_<double>(double x) {
-  const double r = __builtin_amdgcn_rcp(x);    // v_rcp_f64 (quarter rate)
-  const double e = fma(-x, r, 1.0);
-  return fma(r, e, r);   // one Newton step: <= 1 ulp from 1/x (scripts/micro/acc.hip)
-}
-template <> __device__ __forceinline__ float rcp_<float>(float x) {
-  return __builtin_amdgcn_rcpf(x);
-}
-template <class R> __device__ __forceinline__ R exp_(R x);
-// exp for the sweep: reduction by ln2 (hi/lo), Taylor degree 12 on |r| <= ln2/2,
-// ldexp.  n = round(x log2 e) comes from the 1.5*2^52 shifter (its low word is n
-// as an int, fed straight to v_ldexp_f64: no v_rndne / v_cvt_i32_f64, the latter
-// half rate).  x is clamped at -746 (below it exp is 0 either way, and the shifter
-// needs |x log2 e| < 2^51); arguments here are <= 0, underflow ends in 0 via ldexp.
-template <> __device__ __forceinline__ double exp_<double>(double x) {
-  x = fmax(x, -746.0);
-  const double SH = 6755399441055744.0;   // 1.5 * 2^52
-  const double t = fma(x, 1.4426950408889634, SH);
-  const double n = t - SH;
-  const int ni = (int)(uint32_t)__builtin_bit_cast(uint64_t, t);
-  double r = fma(-n, 6.93147180369123816490e-01, x);
-  r = fma(-n, 1.90821492927058770002e-10, r);
-  double p = 2.08767569878680989792e-09;   // 1/12!
-  p = fma(p, r, 2.50521083854417187751e-08);
-  p = fma(p, r, 2.75573192239858906526e-07);
-  p = fma(p, r, 2.75573192239858906526e-06);
-  p = fma(p, r, 2.48015873015873015873e-05);
-  p = fma(p, r, 1.98412698412698412698e-04);
-  p = fma(p, r, 1.38888888888888888889e-03);
-  p = fma(p, r, 8.33333333333333333333e-03);
-  p = fma(p, r, 4.16666666666666666667e-02);
-  p = fma(p, r, 1.66666666666666666667e-01);
-  p = fma(p, r, 0.5);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(p, ni);
-}
-template <> __device__ __forceinline__ float exp_<float>(float x) { return __expf(x); }
-
-// Estrin's scheme for sum_k c[k] t^k (k < N): pairs c[2j] + c[2j+1] t, then pairs of those
-// with t^2, t^4, ...: dependency depth ceil(log2 N) + 1 FMAs instead of N - 1.
-template <int N>
-__device__ __forceinline__ double estrin(const double* c, double t) {
-  constexpr int M = (N + 1) / 2;
-  double v[M];
-#pragma unroll
-  for (int j = 0; j < M; ++j) v[j] = (2 * j + 1 < N) ? fma(c[2 * j + 1], t, c[2 * j]) : c[2 * j];
-  double x = t * t;
-#pragma unroll
-  for (int n = M; n > 1; n = (n + 1) / 2) {
-#pragma unroll
-    for (int j = 0; j < n / 2; ++j) v[j] = fma(v[2 * j + 1], x, v[2 * j]);
-    if (n & 1) v[n / 2] = v[n - 1];
-    x = x * x;
-  }
-  return v[0];
-}
-// exp_<double>'s reduction and Taylor-12 polynomial, the polynomial by Estrin
-__device__ __forceinline__ double exp_lat(double x) {
-  x = fmax(x, -746.0);
-  const double SH = 6755399441055744.0;   // 1.5 * 2^52
-  const double t = fma(x, 1.4426950408889634, SH);
-  const double n = t - SH;
-  const int ni = (int)(uint32_t)__builtin_bit_cast(uint64_t, t);
-  double r = fma(-n, 6.93147180369123816490e-01, x);
-  r = fma(-n, 1.90821492927058770002e-10, r);
-  constexpr double c[13] = {1.0, 1.0, 0.5, 1.66666666666666666667e-01,
-                            4.16666666666666666667e-02, 8.33333333333333333333e-03,
-                            1.38888888888888888889e-03, 1.98412698412698412698e-04,
-                            2.48015873015873015873e-05, 2.75573192239858906526e-06,
-                            2.75573192239858906526e-07, 2.50521083854417187751e-08,
-                            2.08767569878680989792e-09};
-  return ldexp(estrin<13>(c, r), ni);
-}
-// exp_ with a degree-11 polynomial: same reduction, one FMA fewer
-__device__ __forceinline__ double exp11_(double x) {
-  x = fmax(x, -746.0);
-  const double SH = 6755399441055744.0;
-  const double t = fma(x, 1.4426950408889634, SH);
-  const double n = t - SH;
-  const int ni = (int)(uint32_t)__builtin_bit_cast(uint64_t, t);
-  double r = fma(-n, 6.93147180369123816490e-01, x);
-  r = fma(-n, 1.90821492927058770002e-10, r);
-  // degree-11 Chebyshev fit on |r| <= ln2/2 (scripts/micro/exp_fit.py): <= 1 ulp from the
-  // correctly rounded exp, one FMA fewer than Taylor-12
-  double p = 2.5110037605963777e-08;
-  p = fma(p, r, 2.763263963904103e-07);
-  p = fma(p, r, 2.755724091857897e-06);
-  p = fma(p, r, 2.4801485482328494e-05);
-  p = fma(p, r, 0.00019841269890047113);
-  p = fma(p, r, 0.0013888888952314775);
-  p = fma(p, r, 0.008333333333319601);
-  p = fma(p, r, 0.0416666666664881);
-  p = fma(p, r, 0.1666666666666668);
-  p = fma(p, r, 0.5000000000000019);
-  p = fma(p, r, 1.0);
-  p = fma(p, r, 1.0);
-  return ldexp(p, ni);
-}
-
-// Likelihood terms of one bin given its modulation dL (shared by every mode).
-// acc: [0] sum d^2, [1] sum a, [2] sum a e, [3] sum w; returns h (adjoint seed of dL).
-// yi = y / uy is staged per bin (fitoct_api.cpp stage), so d = (y - m) / uy is one FMA,
-// and c x / L is formed once for the exponent and the theta3 weight.
-// The non-physical guard (1 + dL <= 0 -> lp = -inf) is a per-lane running min
-// (umin), applied once after the lane's bins (no per-bin selects).
-template <class R, class A, int NA>
-__device__ __forceinline__ R bin_tail(R iL, R cx, R yi, R isu, R th1, R th2, A (&acc)[NA]) {
-  const R ciL = cx * iL;                                         // c x / L
-  R e;                                                           // exp(-c x / L)
-  if constexpr (sizeof(R) == 8) e = exp11_(-ciL);
-  else e = exp_<R>(-ciL);
-  const R m = fma(th2, e, th1);                                  // ui.R:88
-  const R d = fma(-m, isu, yi);                                  // (y-m)/uy
-  const R a = d * isu;                                           // dlp/dm * sigma^2
-  const R ae = a * e;
-  const R w = ae * ciL;
-  acc[0] += (A)(d * d);
-  acc[1] += (A)a;
-  acc[2] += (A)ae;
-  acc[3] += (A)w;
-  return w * iL;                                                 // dlp/ddL / (th2 th3) * sigma^2
-}
-template <class R, class A, int NA, bool LAT = false>
-__device__ __forceinline__ R bin_core(R u, R cx, R yi, R isu, R th1, R th2, R th3, A (&acc)[NA],
-                                      R& umin) {   // u = 1 + dL
-  umin = fmin(umin, u);
-  const R L = th3 * u;                                           // decay length theta3*(1+dL)
-  const R iL = rcp_<R>(L);
-  const R ciL = cx * iL;                                         // c x / L
-  R e;                                                           // exp(-c x / L)
-  if constexpr (LAT && sizeof(R) == 8) e = exp_lat(-ciL);
-  else e = exp_<R>(-ciL);
-  const R m = fma(th2, e, th1);                                  // ui.R:88
-  const R d = fma(-m, isu, yi);                                  // (y-m)/uy
-  const R a = d * isu;                                           // dlp/dm * sigma^2
-  const R ae = a * e;
-  const R w = ae * ciL;
-  acc[0] += (A)(d * d);
-  acc[1] += (A)a;
-  acc[2] += (A)ae;
-  acc[3] += (A)w;
-  return w * iL;                                                 // dlp/ddL / (th2 th3) * sigma^2
-}
-
-// MODE_POLY: dL = a P(t) with P = sum_l c_l t^l ; moments M_l += h a t^l
-template <class R, int NNP, class A>
-__device__ __forceinline__ void bin_poly(R cx, R y, R isu, R t, R av, R th1, R th2, R th3,
-                                         const R (&cf)[NNP], A (&acc)[4 + NNP], R& umin) {
-  R P = cf[NNP - 1];
-#pragma unroll
-  for (int k = NNP - 2; k >= 0; --k) P = fma(P, t, cf[k]);
-  const R h = bin_core<R, A, 4 + NNP>(fma(av, P, R(1)), cx, y, isu, th1, th2, th3, acc, umin);
-  R p = h * av;
-  acc[4] += (A)p;
-#pragma unroll
-  for (int l = 1; l < NNP; ++l) {
-    p *= t;
-    acc[4 + l] += (A)p;
-  }
-}
-
-// MODE_POLY on a uniform grid: the forward half of bin_poly; returns w = h a,
-// the bin's weight in the moments (accumulated per lane by moments_geo).
-template <class R, int NNP, class A, bool LAT = false>
-__device__ __forceinline__ R bin_poly_fwd(R cx, R y, R isu, R t, R av, R th1, R th2, R th3,
-                                          const R (&cf)[NNP], A (&acc)[4 + NNP], R& umin) {
-  R P;
-  if constexpr (LAT && sizeof(R) == 8) {
-    P = estrin<NNP>(cf, t);
-  } else {
-    P = cf[NNP - 1];
-#pragma unroll
-    for (int k = NNP - 2; k >= 0; --k) P = fma(P, t, cf[k]);
-  }
-  return bin_core<R, A, 4 + NNP, LAT>(fma(av, P, R(1)), cx, y, isu, th1, th2, th3, acc, umin) * av;
-}
-
-// Two bins of bin_poly_fwd sharing one reciprocal: 1/L0 = L1 / (L0 L1), 1/L1 = L0 / (L0 L1)
-// (one quarter-rate v_rcp_f64 and its Newton step for two bins, <= 3 ulp).
-template <class R, int NNP, class A>
-__device__ __forceinline__ void bin_poly_fwd2(R cx0, R y0, R isu0, R t0, R a0, R cx1, R y1,
-                                              R isu1, R t1, R a1, R th1, R th2, R th3,
-                                              const R (&cf)[NNP], A (&acc)[4 + NNP], R& umin,
-                                              R& w0, R& w1) {
-  R P0 = cf[NNP - 1], P1 = cf[NNP - 1];
-#pragma unroll
-  for (int k = NNP - 2; k >= 0; --k) {
-    P0 = fma(P0, t0, cf[k]);
-    P1 = fma(P1, t1, cf[k]);
-  }
-  const R u0 = R(1) + a0 * P0, u1 = R(1) + a1 * P1;
-  umin = fmin(umin, fmin(u0, u1));
-  const R L0 = th3 * u0, L1 = th3 * u1;
-  const R ip = rcp_<R>(L0 * L1);
-  w0 = bin_tail<R, A, 4 + NNP>(ip * L1, cx0, y0, isu0, th1, th2, acc) * a0;
-  w1 = bin_tail<R, A, 4 + NNP>(ip * L0, cx1, y1, isu1, th1, th2, acc) * a1;
-}
-
-// Moments of one lane's BPT bins t_b = t0 R^b:  M_l = t0^l sum_b w_b (R^l)^b.
-// BPT-1 FMAs + 2 multiplies per moment instead of 2 operations per bin and moment.
-template <int BPT, int NNP>
-__device__ __forceinline__ void moments_geo(KPc& P, double t0, const double (&w)[BPT],
-                                            double (&acc)[4 + NNP]) {
-  double pw = 1.0;
-#pragma unroll
-  for (int l = 0; l < NNP; ++l) {
-    const double X = P.geo_R[l];
-    double S = w[BPT - 1];
-#pragma unroll
-    for (int b = BPT - 2; b >= 0; --b) S = fma(S, X, w[b]);
-    acc[4 + l] = pw * S;
-    pw *= t0;
-  }
-}
-
-// The same for one 8-bin half of a 16-bin lane (BPT 16): M_l += t0^l sum_b w_b (R^l)^b.
-template <int NB, int NNP>
-__device__ __forceinline__ void moments_geo_add(KPc& P, double t0, const double (&w)[NB],
-                                                double (&acc)[4 + NNP]) {
-  double pw = 1.0;
-#pragma unroll
-  for (int l = 0; l < NNP; ++l) {
-    const double X = P.geo_R[l];
-    double S = w[NB - 1];
-#pragma unroll
-    for (int b = NB - 2; b >= 0; --b) S = fma(S, X, w[b]);
-    acc[4 + l] = fma(pw, S, acc[4 + l]);
-    pw *= t0;
-  }
-}
-
-// MODE_ROWS / MODE_STREAM: dL = B_i . yGP ; (B^T h)_k += B_ik h
-// LAT (f64, 1-2 bins per lane: a latency-bound sweep): exp by Estrin's scheme (config 5 at
-// one GPU +7 %, config 2 +-0; the dot product in three FMA chains as well measured config 5
-// +10 % but config 2 -1.8 %, alone config 5 -8 %: profiles/r06_ab_rows.txt)
-template <class R, int NNP, class A, bool LAT = false>
-__device__ __forceinline__ void bin_rows(R cx, R y, R isu, const R (&Brow)[NNP], R th1, R th2,
-                                         R th3, const R (&yg)[NNP], A (&acc)[4 + NNP], R& umin) {
-  R dL = R(0);
-#pragma unroll
-  for (int k = 0; k < NNP; ++k) dL = fma(Brow[k], yg[k], dL);
-  const R h = bin_core<R, A, 4 + NNP, LAT>(R(1) + dL, cx, y, isu, th1, th2, th3, acc, umin);
-#pragma unroll
-  for (int k = 0; k < NNP; ++k) acc[4 + k] = fma((A)Brow[k], (A)h, acc[4 + k]);
-}
-
-// Transposed butterfly over the wave: 32 values x 64 lanes -> lane l holds the
-// full sum of value (l >> 1).  Each step halves the live values: lanes whose
-// step bit is set keep the upper half.  Bits 5 and 4 use the gfx950 permlane
-// swaps (no select needed), bits 3..1 DPP row mirrors (partner differs in the
-// step bit and below), the final pair a quad swap.
-template <int H, int CTRL, int NV>
-__device__ __forceinline__ void tr_dpp(double (&v)[NV], bool up) {
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    const double send = up ? v[i] : v[i + H];
-    const double keep = up ? v[i + H] : v[i];
-    v[i] = keep + dpp<CTRL>(send);
-  }
-}
-// The same transposed butterfly for 8 values (U-turn criteria): after it every
-// lane of each 8-lane group holds the full sum of one value; returns whether all
-// 8 sums are > 0 (one ballot).  ~3x fewer cross-lane steps than 8 butterflies.
-__device__ __forceinline__ bool transpose_all_positive8(double (&v)[8], int lane) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) v[i] = swap32_add(v[i], v[i + 4]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i) v[i] = swap16_add(v[i], v[i + 2]);
-  tr_dpp<1, DPP_MIRROR>(v, (lane & 8) != 0);
-  double x = v[0];
-  x += dpp<DPP_XOR1>(x);
-  x += dpp<DPP_XOR2>(x);
-  x += dpp<DPP_HALF_MIRROR>(x);
-  const uint64_t ok = __builtin_amdgcn_ballot_w64(x > 0.0);
-  return ok == __builtin_amdgcn_read_exec();
-}
-
-// The transposed butterfly for any NV <= 32 values: halves the live values per
-// step (ceil).  Returns the lane's total and, in idx, which value it is (-1: a
-// padding lane).
-// A value without a partner at a step belongs to the step's lower lanes alone: its
-// slot in the upper lanes is padding.  A padding slot is only ever sent to, and
-// summed in, padding slots (a lane receives the slot it keeps, whose index is the
-// sender's), and padding lanes store nothing (idx = -1), so what a padding slot
-// holds never reaches a result.  Such a value therefore needs no select and no
-// zero partner: every lane adds its partner's copy to its own, which in the lower
-// lanes is the same keep + received, same operands, same order, as with the
-// selects (each 4 v_cndmask per step), and in the upper lanes a sum nobody reads.
-// No x + 0.0 is formed in a lane that holds a value (before and after this form).
-template <int H, int N, int CTRL, int NV>
-__device__ __forceinline__ void tr_dpp_n(double (&v)[NV], bool up) {
-#pragma unroll
-  for (int i = 0; i < H; ++i) {
-    if (i + H < N) {
-      const double send = up ? v[i] : v[i + H];
-      const double keep = up ? v[i + H] : v[i];
-      v[i] = keep + dpp<CTRL>(send);
-    } else {
-      v[i] = v[i] + dpp<CTRL>(v[i]);
-    }
-  }
-}
-template <int NV>
-__device__ __forceinline__ double transpose_reduce(double (&v)[NV], int lane, int& idx) {
-  constexpr int c1 = (NV + 1) / 2, c2 = (c1 + 1) / 2, c3 = (c2 + 1) / 2, c4 = (c3 + 1) / 2;
-  constexpr int c5 = (c4 + 1) / 2;
-  static_assert(NV <= 32 && c5 == 1, "transpose_reduce: at most 32 values");
-  // (odd NV: the last value's swap partner is the first pair's swapped operand, dead after
-  // its sum, instead of a zero moved into a register pair for it: the lower half gets
-  // a_low + a_high as before, the upper half is a padding slot)
-  double spare = 0.0;
-#pragma unroll
-  for (int i = 0; i < c1; ++i) {
-    if (i == 0 && c1 < NV) v[i] = swap32_add(v[i], v[i + c1], spare);
-    else v[i] = swap32_add(v[i], i + c1 < NV ? v[i + c1] : spare);
-  }
-#pragma unroll
-  for (int i = 0; i < c2; ++i) v[i] = swap16_add(v[i], i + c2 < c1 ? v[i + c2] : 0.0);
-  tr_dpp_n<c3, c2, DPP_MIRROR>(v, (lane & 8) != 0);
-  tr_dpp_n<c4, c3, DPP_HALF_MIRROR>(v, (lane & 4) != 0);
-  tr_dpp_n<c5, c4, DPP_QREV>(v, (lane & 2) != 0);
-  int i = (lane & 2) ? c5 : 0;
-  bool ok = i < c4;
-  i += (lane & 4) ? c4 : 0;
-  ok = ok && i < c3;
-  i += (lane & 8) ? c3 : 0;
-  ok = ok && i < c2;
-  i += (lane & 16) ? c2 : 0;
-  ok = ok && i < c1;
-  i += (lane & 32) ? c1 : 0;
-  ok = ok && i < NV;
-  idx = ok ? i : -1;
-  return v[0] + dpp<DPP_XOR1>(v[0]);
-}
-
-// per-lane resident bin data
-template <class R, int BPT, int NNP, int MODE>
-struct Bins {
-  static constexpr int NB = BPT > 0 ? BPT : 1;
-  static constexpr int NR = MODE == MODE_POLY ? 2 : NNP;
-  R cx[NB], y[NB], isu[NB];
-  R row[NB][NR];
-  __device__ void load(KPc& P, int tid) {
-    if constexpr (BPT > 0) {
-      const AS_GLB R* pcx = (const AS_GLB R*)P.cx;
-      const AS_GLB R* py = (const AS_GLB R*)P.y;
-      const AS_GLB R* pisu = (const AS_GLB R*)P.isu;
-      const AS_GLB R* pB = (const AS_GLB R*)P.B;
-      if constexpr (BPT == 16) {   // compact: y, 1/uy, a per bin; c*x and t of bin 0 only
-        cx[0] = pcx[tid];
-        row[0][0] = pB[2 * (size_t)tid];
-#pragma unroll
-        for (int b = 0; b < BPT; ++b) {
-          const int i = tid + b * GT;
-          y[b] = py[i];
-          isu[b] = pisu[i];
-          row[b][1] = pB[2 * (size_t)i + 1];
-        }
-      } else {
-#pragma unroll
-        for (int b = 0; b < BPT; ++b) {
-          const int i = tid + b * GT;
-          cx[b] = pcx[i];
-          y[b] = py[i];
-          isu[b] = pisu[i];
-#pragma unroll
-          for (int k = 0; k < NR; ++k) row[b][k] = pB[(size_t)i * NR + k];
-        }
-      }
-    }
-  }
-};
-
-// What parameter k's lane needs on every leaf but which depends only on (k, D, Nn, family):
-// fixed for the launch, so one NUTS wave writes it to LDS at start-up (load_kinv, before the
-// tile's first barrier; read only after it) and the leaf path reads it back (a ds_read is no
-// VALU issue) instead of re-deriving it from comparison chains.  Only a role, byte offsets
-// and constant coefficients: every value they select between is still computed per leaf.
-struct LaneRole {
-  double aw;   // horseshoe: weight of the lane's likelihood coefficient (prior_part)
-  double cc;   // horseshoe: the inverse-gamma shape of an r2 lane, 1/2 (global) or nu/2
-  int soff;    // byte offset of the bin sum the lane's gradient needs (finish_grad)
-  int aoff;    // horseshoe: byte offset in AUX of the scale / yGP its coefficient takes
-  int kind;    // horseshoe: RK_Z (a z_j lane), RK_R1 (an r1 lane), RK_R2 (the rest)
-  int pad;
-};
-enum RoleKind : int { RK_Z = 0, RK_R1 = 1, RK_R2 = 2 };
-static_assert(sizeof(LaneRole) == 32, "LaneRole: 32 B per lane");
-
-template <int FAM>
-__device__ __forceinline__ LaneRole lane_role(int k, int D, int Nn, double nu) {
-  LaneRole r;
-  // which bin sum lane k's gradient needs.  Past D (padded lanes) it is not used:
-  // finish_grad forms a gradient only under k < D.
-  int si = 0;
-  if (k < 3) si = 1 + k;
-  else if (k == D - 1) si = 0;
-  else if (k < 3 + Nn) si = 4 + (k - 3);
-  else if (FAM == FAM_HORSESHOE && k >= 5 + Nn && k < D) {
-    // local scale j of r1 (k = 5 + Nn + j) or r2 (k = 5 + 2 Nn + j)
-    const int x = k - 5 - Nn;
-    si = 4 + (x < Nn ? x : x - Nn);
-  }
-  r.soff = si * 8;
-  // the horseshoe's lanes 3 <= k < D - 1 (prior_part), in the forms prior_part used per leaf
-  const bool tz = k < 3 + Nn;
-  const bool r1l = k >= 5 + Nn && k < 5 + 2 * Nn, r2l = k >= 5 + 2 * Nn;
-  const bool tr1 = k == 3 + Nn || r1l;
-  r.cc = (k == 4 + Nn) ? 0.5 : 0.5 * nu;
-  const int ai = tz ? 32 + (k - 3) : r1l ? k - 5 - Nn : r2l ? k - 5 - 2 * Nn : 0;
-  r.aw = (tz || r1l) ? 1.0 : r2l ? 0.5 : 0.0;
-  r.aoff = (ai >= 0 && ai < NAUX ? ai : 0) * 8;   // (other lanes never read it: kept inside AUX)
-  r.kind = tz ? RK_Z : tr1 ? RK_R1 : RK_R2;
-  r.pad = 0;
-  return r;
-}
-
-// LDS carve -----------------------------------------------------------------
-// [ K^-1 (KMAX x KMAX, row stride NNP) | b (KMAX) | LaneRole[VLEN] | MP[GMAX][MPW] |
-//   PART[G][NGW][NSLOT] |
-//   G x chain{ ChainScalars | NVEC vectors | SUMS[NSLOT] | AUX[NAUX] | levels[max_depth][NLVL] } ]
-template <int PPL>
-struct Lds {
-  static constexpr int VLEN = WAVE * PPL;
-  static constexpr int KBYTES = (KMAX * KMAX + KMAX) * 8;
-  static constexpr int RBYTES = VLEN * (int)sizeof(LaneRole);   // the lane-role block, after b
-  static __host__ __device__ constexpr int head_bytes(int G) {
-    return KBYTES + RBYTES + (GMAX * MPW + NGW * G * NSLOT) * 8;
-  }
-  static __host__ __device__ constexpr int chain_bytes(int max_depth) {
-    // ... | levels[max_depth][NLVL][VLEN] | merge-uniform rings[max_depth][WAVE]
-    return (int)sizeof(ChainScalars) +
-           (NVEC * VLEN + NSLOT + NAUX + max_depth * NLVL * VLEN + max_depth * WAVE) * 8;
-  }
-  // tiles of one or two chains (deep speculation): per chain, the booked leaf's q,
-  // end-updated p, g, lp and sum r^2, handed from the chain's wave to its helper wave
-  static constexpr int HX_BYTES = ((3 * VLEN + 2) * 8 + 15) / 16 * 16;
-  // two-ended trajectories (G = 3 areas: the chain's, two producers'): per producer, two
-  // slots for the leaves it hands its booking helper (q, end-updated p, g, lp, sum r^2, depth,
-  // leaf, transition)
-  static constexpr int PX_BYTES = ((3 * VLEN + 8) * 8 + 15) / 16 * 16;
-  // ... and per end, two slots for its subtree records (Chain::rvec): 5 vectors, 16 scalars
-  // (one parameter per lane; at two, whose chain areas leave less room, one record slot per
-  // end in the producer's own area)
-  static constexpr int QX_DOUBLES = 5 * VLEN + 16;
-  static constexpr int QX_SLOTS = PPL == 1 ? 4 : 0;
-  static __host__ __device__ constexpr int bytes(int G, int max_depth) {
-    return head_bytes(G) + G * chain_bytes(max_depth) +
-           (G <= 2 ? G * HX_BYTES : G == 3 ? 4 * PX_BYTES + QX_SLOTS * QX_DOUBLES * 8 : 0);
-  }
-  AS_LDS char* base;
-  int G, cb;
-  __device__ AS_LDS double* kinv() const { return (AS_LDS double*)base; }
-  __device__ AS_LDS double* bv() const { return (AS_LDS double*)base + KMAX * KMAX; }
-  __device__ AS_LDS LaneRole* lane_roles() const { return (AS_LDS LaneRole*)(base + KBYTES); }
-  __device__ AS_LDS double* mp(int c) const {
-    return (AS_LDS double*)(base + KBYTES + RBYTES) + c * MPW;
-  }
-  __device__ AS_LDS double* part() const {
-    return (AS_LDS double*)(base + KBYTES + RBYTES) + GMAX * MPW;
-  }
-  __device__ AS_LDS char* chain(int c) const { return base + head_bytes(G) + c * cb; }
-  __device__ AS_LDS ChainScalars& cs(int c) const { return *(AS_LDS ChainScalars*)chain(c); }
-  __device__ AS_LDS double* vecs(int c) const {
-    return (AS_LDS double*)(chain(c) + sizeof(ChainScalars));
-  }
-  __device__ AS_LDS double* sums(int c) const { return vecs(c) + NVEC * VLEN; }
-  __device__ AS_LDS double* aux(int c) const { return sums(c) + NSLOT; }
-  __device__ AS_LDS double* lvls(int c) const { return aux(c) + NAUX; }
-  // chain c's hand-off block (G <= 2)
-  __device__ AS_LDS double* hx(int c = 0) const {
-    return (AS_LDS double*)(base + head_bytes(G) + G * cb + c * HX_BYTES);
-  }
-  // producer s's hand-off slot k (two-ended trajectories, G = 3)
-  __device__ AS_LDS double* px(int s, int k) const {
-    return (AS_LDS double*)(base + head_bytes(G) + G * cb + (2 * s + k) * PX_BYTES);
-  }
-  // the record slots (end s, slot k = 2 s + k), after the hand-off slots
-  __device__ AS_LDS double* qx0() const {
-    return (AS_LDS double*)(base + head_bytes(G) + G * cb + 4 * PX_BYTES);
-  }
-};
-
-// The likelihood sweep of chains [cb, ce) of the tile (gradient waves only).
-// PART[c][wave][0 .. 4+NNP) receives this wave's partial sums of chain c.
-// LATR: the row-mode sweep's latency form (bin_rows LAT); every sampler and the logp kernel
-// use it, so all paths keep computing the same gradient bit for bit.
-template <class R, int BPT, int NNP, int MODE, bool LATR = false>
-__device__ void gradient_pass(KPc& P, const Bins<R, BPT, NNP, MODE>& bins,
-                              const AS_LDS double* mpall, AS_LDS double* part, const int* done,
-                              int cb, int ce,
-                              int tid, int lane, int wave) {
-  FITOCT_MARK(gradient_pass);
-  for (int c = cb; c < ce; ++c) {
-    if (done[c]) continue;   // wave-uniform (LDS broadcast)
-    const AS_LDS double* mp = mpall + c * MPW;
-    const R th1 = (R)mp[0], th2 = (R)mp[1], th3 = (R)mp[2];
-    R cf[NNP];   // POLY: c_l = b_l (K^-1 yGP)_l ; ROWS: yGP_k
-#pragma unroll
-    for (int k = 0; k < NNP; ++k) cf[k] = (R)mp[4 + k];
-    double acc[4 + NNP];
-#pragma unroll
-    for (int k = 0; k < 4 + NNP; ++k) acc[k] = 0.0;
-    R umin = R(1);
-    if constexpr (BPT == 16) {   // MODE_POLY f64 on an arithmetic grid (host-checked)
-      double cx0 = bins.cx[0], t0 = bins.row[0][0];
-      const double tmax = P.geo_tmax;
-      // opaque per sweep: c*x_b and t_b are formed inside the sweep, as the compact layout
-      // intends, instead of being hoisted out of the sweep loop (32 more live doubles)
-      asm volatile("" : "+v"(cx0), "+v"(t0));
-      // the lane's bins in groups of NQ (moments per group: NQ weights live at a time);
-      // one reciprocal per bin (pairs sharing one measured 3 % slower here)
-      constexpr int NQ = BPT16_GROUP;
-#pragma unroll
-      for (int q = 0; q < 16 / NQ; ++q) {
-        double w[NQ];
-#pragma unroll
-        for (int b = 0; b < NQ; ++b) {
-          const int bb = q * NQ + b;
-          const double cxb = cx0 + P.geo_dcx[bb];
-          const double tb = fmin(t0 * P.geo_R[bb], tmax);
-          w[b] = bin_poly_fwd<R, NNP, double>(cxb, bins.y[bb], bins.isu[bb], tb,
-                                              bins.row[bb][1], th1, th2, th3, cf, acc, umin);
-        }
-        moments_geo_add<NQ, NNP>(P, q ? t0 * P.geo_R[q * NQ] : t0, w, acc);
-      }
-    } else if constexpr (BPT > 0 && MODE == MODE_POLY && sizeof(R) == 8) {
-      if (P.geo) {
-        double w[BPT];
-        // 8 bins per lane (the headline shape, N = 2048): bins in pairs sharing one
-        // reciprocal, exp by a degree-11 polynomial (A/B: config 3 +1.7 %, configs 2 / 5
-        // within noise; at 16 bins the pairs spill)
-        if constexpr (BPT == 8) {
-#pragma unroll
-          for (int b = 0; b < BPT; b += 2)
-            bin_poly_fwd2<R, NNP, double>(bins.cx[b], bins.y[b], bins.isu[b], bins.row[b][0],
-                                          bins.row[b][1], bins.cx[b + 1], bins.y[b + 1],
-                                          bins.isu[b + 1], bins.row[b + 1][0], bins.row[b + 1][1],
-                                          th1, th2, th3, cf, acc, umin, w[b], w[b + 1]);
-        } else {
-          // sweeps of at most 2 bins per lane (N <= 512: configs 2 and 5) are latency-bound:
-          // the basis polynomial and exp by Estrin's scheme (config 5 +1.8 %)
-          constexpr bool LAT = BPT <= 2;
-#pragma unroll
-          for (int b = 0; b < BPT; ++b)
-            w[b] = bin_poly_fwd<R, NNP, double, LAT>(bins.cx[b], bins.y[b], bins.isu[b],
-                                                     bins.row[b][0], bins.row[b][1], th1, th2,
-                                                     th3, cf, acc, umin);
-        }
-        moments_geo<BPT, NNP>(P, bins.row[0][0], w, acc);
-      } else {
-#pragma unroll
-        for (int b = 0; b < BPT; ++b)
-          bin_poly<R, NNP, double>(bins.cx[b], bins.y[b], bins.isu[b], bins.row[b][0],
-                                   bins.row[b][1], th1, th2, th3, cf, acc, umin);
-      }
-    } else if constexpr (BPT > 0 && MODE == MODE_POLY) {
-#pragma unroll
-      for (int b = 0; b < BPT; ++b)
-        bin_poly<R, NNP, double>(bins.cx[b], bins.y[b], bins.isu[b], bins.row[b][0],
-                                 bins.row[b][1], th1, th2, th3, cf, acc, umin);
-    } else if constexpr (BPT > 0) {
-      // the few bins of one lane accumulate in R, the lane totals in f64
-      constexpr bool ROWS_LAT = LATR && sizeof(R) == 8 && BPT <= 2;
-      R racc[4 + NNP];
-#pragma unroll
-      for (int k = 0; k < 4 + NNP; ++k) racc[k] = R(0);
-#pragma unroll
-      for (int b = 0; b < BPT; ++b)
-        bin_rows<R, NNP, R, ROWS_LAT>(bins.cx[b], bins.y[b], bins.isu[b], bins.row[b], th1, th2,
-                                      th3, cf, racc, umin);
-#pragma unroll
-      for (int k = 0; k < 4 + NNP; ++k) acc[k] = (double)racc[k];
-    } else {
-      const AS_GLB R* pcx = (const AS_GLB R*)P.cx;
-      const AS_GLB R* py = (const AS_GLB R*)P.y;
-      const AS_GLB R* pisu = (const AS_GLB R*)P.isu;
-      const AS_GLB R* pB = (const AS_GLB R*)P.B;
-      for (int i = tid; i < P.n_pad; i += GT) {
-        if constexpr (MODE == MODE_POLY) {
-          bin_poly<R, NNP, double>(pcx[i], py[i], pisu[i], pB[2 * (size_t)i], pB[2 * (size_t)i + 1],
-                                   th1, th2, th3, cf, acc, umin);
-        } else {
-          R row[NNP];
-#pragma unroll
-          for (int k = 0; k < NNP; ++k) row[k] = pB[(size_t)i * NNP + k];
-          bin_rows<R, NNP, double>(pcx[i], py[i], pisu[i], row, th1, th2, th3, cf, acc, umin);
-        }
-      }
-    }
-    if (!(umin > R(0))) acc[0] = INFINITY;   // some bin has 1 + dL <= 0: lp = -inf
-    int idx;
-    FITOCT_MARK(sweep_reduce);
-    const double r = transpose_reduce<4 + NNP>(acc, lane, idx);
-    if (!(lane & 1) && idx >= 0) part[(c * NGW + wave) * NSLOT + idx] = r;
-  }
-}
+#include "sweep_math.h"
+#include "lds_layout.h"
+#include "gradient_pass.h"
 
 // (end of the sweep's arithmetic: the sampler's code below keeps HIP's default contraction)
 #pragma clang fp contract(fast)
@@ -2081,6 +1052,37 @@ struct Chain {
     return r == LB_END ? A_SPEC_DISCARD : A_SPEC_WAIT;
   }
 
+  // ---- the two steps of a leaf's booking that have one copy for every path (sub_leaf,
+  // leaf_book, leaf_book_split, book_leaf): the leaf's energy and the push of a level's
+  // record.  (The U-turn checks and the multinomial merge are still written out per path.)
+  // a leaf's Hamiltonian -lp + K(p); NaN counts as +inf (a divergence)
+  __device__ __forceinline__ double leaf_h(const double lp, const V& p, const V& minv) const {
+    double h = -lp + kin(p, minv);
+    if (isnan(h)) h = INFINITY;
+    return h;
+  }
+  // ... and its multinomial weight exp(H0 - h), booked for leaf_book_split (spec_h, spec_w*)
+  __device__ __forceinline__ void spec_weight(const double lp, const V& pe, const V& minv) const {
+    const double h = leaf_h(lp, pe, minv);
+    const XF w = xf_exp(Sp->H0 - h);
+    Sp->spec_h = h;
+    Sp->spec_wm = w.m;
+    Sp->spec_we = w.e;
+  }
+  // push the running subtree T as level l's record (the init subtree of level l + 1); its
+  // proposal, if it is still the leaf (q, g) itself (Tprop < 0), goes to the pool
+  __device__ __forceinline__ void push_level(const int l, const V& Tpb, const V& p, const V& Trho,
+                                             const XF Tw, const int Tprop, unsigned& used,
+                                             const V& q, const V& g, const double cur_lp,
+                                             const double cur_s2, const double h) const {
+    lst(l, K_PBEG, Tpb);
+    lst(l, K_PEND, p);
+    lst(l, K_RHO, Trho);
+    Sp->st_w_m[l] = Tw.m;
+    Sp->st_w_e[l] = Tw.e;
+    Sp->st_prop[l] = (Tprop < 0) ? pool_put(used, q, g, cur_lp, cur_s2, h) : Tprop;
+  }
+
   // Deep speculation, run by the helper wave: the whole bookkeeping of the leaf the chain's
   // wave handed over in HX (act_spec_book's work with the weight computed here), with the
   // coordinates (depth, leaf, direction, step) in Sp advanced for the next leaf exactly as
@@ -2102,12 +1104,7 @@ struct Chain {
     const uint32_t t = (uint32_t)uni(Sp->t);
     tree_uniforms(d, j, t);
     const V minv = ld(V_MINV);
-    double h = -lp + kin(pe, minv);
-    if (isnan(h)) h = INFINITY;
-    const XF w = xf_exp(Sp->H0 - h);
-    Sp->spec_h = h;
-    Sp->spec_wm = w.m;
-    Sp->spec_we = w.e;
+    spec_weight(lp, pe, minv);
     const int r = leaf_book_split(q, pe, g, minv, lp, s2);
     if (r == LB_NEXT) {   // act_begin_subtree's bookkeeping for the subtree of depth d + 1
       const int dirn = (uniform(key, t, TAG_DIR, (uint32_t)(d + 1), 0u) > 0.5) ? 1 : 0;
@@ -2339,8 +1336,7 @@ struct Chain {
     unsigned used = (unsigned)uni(Sp->pool_used);
     Sp->n_leapfrog = nlf + 1;
     tree_uniforms(d, j, (uint32_t)uni(Sp->t));   // this leaf's merge uniforms
-    double h = -cur_lp + kin(p, minv);
-    if (isnan(h)) h = INFINITY;
+    const double h = leaf_h(cur_lp, p, minv);
     const double wl = H0 - h;
     const XF wleaf = xf_exp(wl);
     Sp->sub_metro = sub_metro0 + ((wl > 0.0) ? 1.0 : xf_val(wleaf));
@@ -2354,12 +1350,7 @@ struct Chain {
 #pragma unroll 1
     for (int l = 0; l < d; ++l) {
       if (((j >> l) & 1) == 0) {   // push T as the init subtree of level l+1
-        lst(l, K_PBEG, Tpb);
-        lst(l, K_PEND, p);
-        lst(l, K_RHO, Trho);
-        Sp->st_w_m[l] = Tw.m;
-        Sp->st_w_e[l] = Tw.e;
-        Sp->st_prop[l] = (Tprop < 0) ? pool_put(used, q, g, cur_lp, cur_s2, h) : Tprop;
+        push_level(l, Tpb, p, Trho, Tw, Tprop, used, q, g, cur_lp, cur_s2, h);
         break;
       }
       // merge init I = level l with final T (base_nuts::build_tree at depth l+1)
@@ -2452,15 +1443,10 @@ struct Chain {
   }
 
   // run by the helper wave for the leaf being booked: its Hamiltonian and multinomial
-  // weight, the same operations as leaf_book's first lines
+  // weight (leaf_book's first lines: leaf_h)
   __device__ void spec_weight() const {
     const V pe = ld(V_CUR_G), minv = ld(V_MINV);   // leaf_spec staged the momentum there
-    double h = -Sp->cur_lp + kin(pe, minv);
-    if (isnan(h)) h = INFINITY;
-    const XF w = xf_exp(Sp->H0 - h);
-    Sp->spec_h = h;
-    Sp->spec_wm = w.m;
-    Sp->spec_we = w.e;
+    spec_weight(Sp->cur_lp, pe, minv);
   }
 
   // base_nuts::transition's merge of the completed subtree of depth d (final weight Tw,
@@ -2601,12 +1587,7 @@ struct Chain {
       return LB_END;
     }
     if (nm < d) {   // push the running subtree as the init subtree of level nm + 1
-      lst(nm, K_PBEG, Tpb);
-      lst(nm, K_PEND, p);
-      lst(nm, K_RHO, Trho);
-      Sp->st_w_m[nm] = Tw.m;
-      Sp->st_w_e[nm] = Tw.e;
-      Sp->st_prop[nm] = (Tprop < 0) ? pool_put(used, q, g, cur_lp, cur_s2, h) : Tprop;
+      push_level(nm, Tpb, p, Trho, Tw, Tprop, used, q, g, cur_lp, cur_s2, h);
     }
     sub(0, ts);
     if (!last) {
@@ -2636,8 +1617,7 @@ struct Chain {
     const int d = uni(Sp->depth), j = uni(Sp->leaf), nlf = uni(Sp->n_leapfrog);
     unsigned used = (unsigned)uni(Sp->pool_used);
     Sp->n_leapfrog = nlf + 1;
-    double h = -cur_lp + kin(p, minv);
-    if (isnan(h)) h = INFINITY;
+    const double h = leaf_h(cur_lp, p, minv);
     sub(0, ts);
     const double wl = H0 - h;
     const XF wleaf = xf_exp(wl);
@@ -2659,12 +1639,7 @@ struct Chain {
 #pragma unroll 1
     for (int l = 0; l < d; ++l) {
       if (((j >> l) & 1) == 0) {   // push T as the init subtree of level l+1
-        lst(l, K_PBEG, Tpb);
-        lst(l, K_PEND, p);
-        lst(l, K_RHO, Trho);
-        Sp->st_w_m[l] = Tw.m;
-        Sp->st_w_e[l] = Tw.e;
-        Sp->st_prop[l] = (Tprop < 0) ? pool_put(used, q, g, cur_lp, cur_s2, h) : Tprop;
+        push_level(l, Tpb, p, Trho, Tw, Tprop, used, q, g, cur_lp, cur_s2, h);
         break;
       }
       // merge init I = level l with final T (base_nuts::build_tree at depth l+1)
@@ -2844,11 +1819,11 @@ struct Chain {
     Sp->t += 1;
     const int t = uni(Sp->t);
     // transitions done, for fitoct_plan_poll (replaces rstan's stan.log progress)
-    if (Pr().progress != nullptr && lane == 0) sys_store(Pr().progress + lc, t);
+    if (Pr().progress != nullptr && lane == 0) host_st(Pr().progress + lc, t);
     if (t == Pr().warmup && Pr().adapt && Pr().warmup > 0) Sp->eps = exp(Sp->x_bar);  // complete_adaptation
     if (t >= Pr().warmup + Pr().samples) return A_FINISH;
     // fitoct_plan_cancel: stop at a transition boundary (checked every 8th transition)
-    if (Pr().cancel != nullptr && (t & 7) == 0 && uni(sys_load(Pr().cancel)) != 0) {
+    if (Pr().cancel != nullptr && (t & 7) == 0 && uni(host_ld(Pr().cancel)) != 0) {
       Sp->status = ERR_CANCELLED;
       return A_FINISH;
     }

@@ -1,6 +1,6 @@
 // The launch schedule (schedule.h): the single place where the sampler variant of a launch
 // is decided.  Pure host arithmetic over the shape and the switches; the only functions
-// called are lds_bytes (the kernel's LDS carve, nuts_device.hip) and pair_grid.
+// called are lds_bytes (the kernel's LDS carve, lds_layout.h) and pair_grid.
 #include "schedule.h"
 
 #include <stdlib.h>

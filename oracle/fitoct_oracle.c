@@ -387,7 +387,7 @@ static void leapfrog(nuts_ctx* c, ps_point* z, double e) {
 /* Multinomial weights exp(H0 - H) as extended-exponent floats m * 2^e
  * (m in [1/2, 1) or 0).  Stan keeps log weights and merges them with
  * log_sum_exp; the linear form is the same arithmetic up to rounding, cannot
- * overflow, and is what the HIP sampler uses (nuts_device.hip, struct XF), so
+ * overflow, and is what the HIP sampler uses (wave_math.h, struct XF), so
  * both take the same merge decisions. */
 typedef struct {
   double m;

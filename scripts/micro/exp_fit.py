@@ -1,5 +1,5 @@
 """Degree-11 Chebyshev fit of exp on |r| <= ln2/2 (the coefficients of
-nuts_device.hip::exp_poly) and its ulp check against expl (gcc, host).
+sweep_math.h's exp11_) and its ulp check against expl (gcc, host).
 
     python scripts/micro/exp_fit.py
 """
