@@ -645,6 +645,21 @@ typedef struct {
   const double *q, *eps, *minv;
 } warm_init;
 
+/* one output row [D + 8]: the sampler columns, the constrained parameters, br */
+static void write_row(double* rec, const model* m, const ps_point* z, const trans_info* info,
+                      double eps) {
+  const int D = m->D, Nn = m->Nn;
+  rec[0] = z->lp;
+  rec[1] = info->accept;
+  rec[2] = eps;
+  rec[3] = info->depth;
+  rec[4] = info->n_leapfrog;
+  rec[5] = info->divergent;
+  rec[6] = info->energy;
+  for (int k = 0; k < D; ++k) rec[7 + k] = (k < 3 || k >= 3 + Nn) ? exp(z->q[k]) : z->q[k];
+  rec[7 + D] = m->prior_PD ? NAN : z->s2 / m->N;
+}
+
 /* one chain: init, adaptation (adapt_diag_e_nuts), sampling */
 static int run_chain(const model* m, const fitoct_config* cfg, const warm_init* wi, int lc,
                      double* draws, int ncols, int iters_saved, double* out_eps, double* out_minv,
@@ -715,16 +730,7 @@ static int run_chain(const model* m, const fitoct_config* cfg, const warm_init* 
     lf += info.n_leapfrog;
     if (t >= W || cfg->save_warmup) {
       const int it = cfg->save_warmup ? t : t - W;
-      double* rec = draws + ((size_t)lc * iters_saved + it) * ncols;
-      rec[0] = z.lp;
-      rec[1] = info.accept;
-      rec[2] = eps;
-      rec[3] = info.depth;
-      rec[4] = info.n_leapfrog;
-      rec[5] = info.divergent;
-      rec[6] = info.energy;
-      for (int k = 0; k < D; ++k) rec[7 + k] = (k < 3 || k >= 3 + Nn) ? exp(z.q[k]) : z.q[k];
-      rec[7 + D] = m->prior_PD ? NAN : z.s2 / m->N;
+      write_row(draws + ((size_t)lc * iters_saved + it) * ncols, m, &z, &info, eps);
     }
     if (t < W && cfg->adapt_engaged) {
       /* stepsize_adaptation::learn_stepsize */
@@ -794,11 +800,21 @@ int oracle_logp_grad(const fitoct_problem* p, int n_points, const double* q, dou
                      double* grad, double* sumr2) {
   model m;
   if (model_init(&m, p)) return -1;
-  double* work = (double*)malloc(sizeof(double) * 3 * (p->Nn + 1));
-  for (int i = 0; i < n_points; ++i)
-    lp[i] = logp_grad(&m, q + (size_t)i * m.D, grad + (size_t)i * m.D, sumr2 ? sumr2 + i : NULL,
-                      work);
-  free(work);
+  /* points are independent: threads over them once there are enough to pay (the row audit
+   * of tests/replay_audit.py evaluates every stored row of a run) */
+#ifdef _OPENMP
+#pragma omp parallel if (n_points >= 256)
+#endif
+  {
+    double* work = (double*)malloc(sizeof(double) * 3 * (p->Nn + 1));
+#ifdef _OPENMP
+#pragma omp for schedule(static)
+#endif
+    for (int i = 0; i < n_points; ++i)
+      lp[i] = logp_grad(&m, q + (size_t)i * m.D, grad + (size_t)i * m.D,
+                        sumr2 ? sumr2 + i : NULL, work);
+    free(work);
+  }
   free(m.B);
   return 0;
 }
@@ -845,4 +861,93 @@ int oracle_sample(const fitoct_problem* p, const fitoct_config* cfg, double* dra
                   double* stepsize, double* inv_metric, long long* leapfrogs, int nthreads) {
   return oracle_sample_init(p, cfg, draws, stepsize, inv_metric, leapfrogs, nthreads, NULL, NULL,
                             NULL);
+}
+
+/* ------------------------------------------------------------------------ */
+/* replay: one transition (or one step-size search) from a given state        */
+/* ------------------------------------------------------------------------ */
+/* A NUTS transition is a pure function of (chain id, iteration, start position, step
+ * size, inverse metric, Philox key).  Item i of a replay is chain gid[i] (the GLOBAL chain
+ * id: cfg->chain_offset is not added) at iteration t[i], started at the unconstrained
+ * position q[i][D] with step size eps[i] and inverse metric minv[i][D].  No state is kept
+ * between items or calls.  tests/replay_audit.py replays a sampler's stored transitions
+ * one by one from the sampler's own previous draw. */
+static void replay_ctx(nuts_ctx* c, ps_point* z, const model* m, const fitoct_config* cfg,
+                       uint32_t gid, const double* q, const double* minv) {
+  const int D = m->D;
+  memset(c, 0, sizeof *c);
+  c->m = m;
+  c->D = D;
+  c->key = chain_key(cfg->seed, gid);
+  c->minv = (double*)malloc(sizeof(double) * D);
+  c->work = (double*)malloc(sizeof(double) * 3 * (m->Nn + 1));
+  pt_alloc(&c->z, D);
+  pt_alloc(z, D);
+  memcpy(c->minv, minv, sizeof(double) * D);
+  memcpy(z->q, q, sizeof(double) * D);
+  z->lp = logp_grad(m, z->q, z->g, &z->s2, c->work);
+}
+static void replay_free(nuts_ctx* c, ps_point* z) {
+  free(c->minv);
+  free(c->work);
+  pt_free(&c->z);
+  pt_free(z);
+}
+
+/* rows[n][D + 8]: the row run_chain would store for that transition */
+int oracle_replay(const fitoct_problem* p, const fitoct_config* cfg, int n, const int32_t* gid,
+                  const int32_t* t, const double* q, const double* eps, const double* minv,
+                  double* rows, int nthreads) {
+  model m;
+  if (model_init(&m, p)) return -1;
+  const int D = m.D, ncols = D + 8;
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+#pragma omp parallel for schedule(dynamic, 4)
+#endif
+  for (int i = 0; i < n; ++i) {
+    nuts_ctx c;
+    ps_point z;
+    replay_ctx(&c, &z, &m, cfg, (uint32_t)gid[i], q + (size_t)i * D, minv + (size_t)i * D);
+    c.t = (uint32_t)t[i];
+    c.eps = eps[i];
+    trans_info info;
+    transition(&c, &z, cfg->max_treedepth, &info);
+    write_row(rows + (size_t)i * ncols, &m, &z, &info, eps[i]);
+    replay_free(&c, &z);
+  }
+  (void)nthreads;
+  free(m.B);
+  return 0;
+}
+
+/* init_stepsize() of chain gid[i] for its window[i]-th search (0: before the first
+ * transition, k: after the k-th metric update) from position q[i], incoming step size
+ * eps_in[i] and metric minv[i]; eps_out[i] = the step size found.  Returns the lowest
+ * status of the searches. */
+int oracle_replay_init_stepsize(const fitoct_problem* p, const fitoct_config* cfg, int n,
+                                const int32_t* gid, const int32_t* window, const double* q,
+                                const double* eps_in, const double* minv, double* eps_out,
+                                int nthreads) {
+  model m;
+  if (model_init(&m, p)) return -1;
+  const int D = m.D;
+  int rc_all = 0;
+#ifdef _OPENMP
+  if (nthreads > 0) omp_set_num_threads(nthreads);
+#pragma omp parallel for schedule(dynamic, 4) reduction(min : rc_all)
+#endif
+  for (int i = 0; i < n; ++i) {
+    nuts_ctx c;
+    ps_point z;
+    replay_ctx(&c, &z, &m, cfg, (uint32_t)gid[i], q + (size_t)i * D, minv + (size_t)i * D);
+    double e = eps_in[i];
+    const int rc = init_stepsize(&c, &z, (uint32_t)window[i], &e);
+    eps_out[i] = e;
+    if (rc < rc_all) rc_all = rc;
+    replay_free(&c, &z);
+  }
+  (void)nthreads;
+  free(m.B);
+  return rc_all;
 }

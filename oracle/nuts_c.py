@@ -50,6 +50,11 @@ def lib():
                                      C.c_int, dp]
         L.oracle_sample_init.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.Config), dp, dp,
                                          dp, C.POINTER(C.c_longlong), C.c_int, dp, dp, dp]
+        ip = C.POINTER(C.c_int32)
+        L.oracle_replay.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.Config), C.c_int, ip, ip,
+                                    dp, dp, dp, dp, C.c_int]
+        L.oracle_replay_init_stepsize.argtypes = [C.POINTER(abi.Problem), C.POINTER(abi.Config),
+                                                  C.c_int, ip, ip, dp, dp, dp, dp, C.c_int]
         _L = L
     return _L
 
@@ -108,3 +113,42 @@ def sample(prob, cfg, nthreads: int = 0, q_init=None, init_stepsize=None, init_i
     if rc != 0:
         raise RuntimeError(f"oracle_sample failed with status {rc}")
     return {"draws": draws, "stepsize": eps, "inv_metric": minv, "leapfrogs": lf}
+
+
+def _replay_args(prob, gid, idx, q, eps, minv):
+    gid = np.ascontiguousarray(gid, dtype=np.int32)
+    n = gid.size
+    idx = np.ascontiguousarray(np.broadcast_to(np.asarray(idx, dtype=np.int32), (n,)))
+    q = np.ascontiguousarray(q, dtype=np.float64).reshape(n, prob.D)
+    eps = np.ascontiguousarray(np.broadcast_to(np.asarray(eps, dtype=np.float64), (n,)))
+    minv = np.ascontiguousarray(np.broadcast_to(np.asarray(minv, dtype=np.float64), (n, prob.D)))
+    ip = C.POINTER(C.c_int32)
+    return n, gid, idx, q, eps, minv, [gid.ctypes.data_as(ip), idx.ctypes.data_as(ip), _dp(q),
+                                       _dp(eps), _dp(minv)]
+
+
+def replay(prob, cfg, gid, t, q, eps, minv, nthreads: int = 0):
+    """One transition per item: GLOBAL chain id gid[n] at iteration t[n] from the
+    unconstrained position q[n, D] with step size eps[n] and inverse metric minv[n, D]
+    -> rows[n, D + 8], each the row a run would store for that transition."""
+    n, *keep, ptrs = _replay_args(prob, gid, t, q, eps, minv)
+    rows = np.full((n, prob.D + 8), np.nan)
+    p, c = prob.to_c(), cfg.to_c()
+    rc = lib().oracle_replay(C.byref(p), C.byref(c), n, *ptrs, _dp(rows), int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"oracle_replay failed with status {rc}")
+    return rows
+
+
+def replay_init_stepsize(prob, cfg, gid, window, q, eps, minv, nthreads: int = 0):
+    """The step-size search of chain gid[n] for its window[n]-th search (0: the run's
+    start, k: after the k-th metric update) from position q[n, D], incoming step size
+    eps[n] and inverse metric minv[n, D] -> the step sizes found [n]."""
+    n, *keep, ptrs = _replay_args(prob, gid, window, q, eps, minv)
+    out = np.full(n, np.nan)
+    p, c = prob.to_c(), cfg.to_c()
+    rc = lib().oracle_replay_init_stepsize(C.byref(p), C.byref(c), n, *ptrs, _dp(out),
+                                           int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"oracle_replay_init_stepsize failed with status {rc}")
+    return out

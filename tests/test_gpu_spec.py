@@ -143,25 +143,41 @@ def test_headline_tiles_fit_four_chains_at_depth_12():
             assert pl.info["sampler"] == 3 and pl.info["lds_bytes"] <= 160 * 1024
 
 
-@pytest.mark.parametrize("family,N,Nn,depth", [
-    ("normal", 512, 15, 10), ("normal", 512, 15, 4), ("horseshoe", 2048, 15, 8),
-    ("lasso", 300, 15, 12), ("horseshoe", 2048, 15, 10),
+_TWO_ENDED = [
+    ("normal", 512, 15, 10, None), ("normal", 512, 15, 4, None), ("horseshoe", 2048, 15, 8, None),
+    ("lasso", 300, 15, 12, None), ("horseshoe", 2048, 15, 10, None),
     # Nn = 20: two parameters per lane (the ppl = 2 chain areas), shallow enough to fit
-    ("normal", 512, 20, 6)])
-def test_two_ended_trajectories_preserve_draws_bitwise(family, N, Nn, depth):
+    ("normal", 512, 20, 6, None),
+    # the other row-mode instantiations, whose chain's wave books the forward end too: the
+    # f32 sweep (resident rows) and a caller's basis (f64 rows streamed at N = 1000)
+    ("normal", 1024, 12, 10, "mixed"), ("normal", 300, 15, 10, "mixed"),
+    ("lasso", 1000, 12, 10, "userB"), ("lasso", 300, 12, 10, "userB")]
+
+
+@pytest.mark.parametrize("family,N,Nn,depth,variant", _TWO_ENDED,
+                         ids=["-".join(str(v) for v in c if v is not None) for c in _TWO_ENDED])
+def test_two_ended_trajectories_preserve_draws_bitwise(family, N, Nn, depth, variant):
     """Tiles of one chain grow both ends of each trajectory at once: two producer waves build
     the subtrees of each direction whole (weights, merges, U-turn checks, proposal) in chain
     areas of their own and hand the chain's wave one record per subtree, which it books at the
     trajectory level in Stan's tree order (nuts_device.hip "two-ended trajectories").  Same
     draws, step sizes, metrics and leapfrog counts as the one-ended deep-speculation path
-    (FITOCT_NO_BIDI=1), with trees cut at max_treedepth 4 and the ppl = 2 carve (Nn = 20).
+    (FITOCT_NO_BIDI=1), with trees cut at max_treedepth 4 and the ppl = 2 carve (Nn = 20),
+    in mixed precision and with a caller-supplied basis (test_gpu_logp's non-SE B).
     The plan reports the mode and its records in flight per end (ABI 7: one).  With up to
     128 such tiles on the chip the tiles are also paired (test_gpu_pair.py); here both."""
-    prob = _prob(family, N, Nn)
-    cfg = SamplerConfig(chains=24, warmup=80, samples=60, seed=35, max_treedepth=depth)
+    if variant == "userB":
+        from replay_cases import user_basis_prob
+        prob = user_basis_prob(N)
+        assert (prob.prior_type, prob.Nn) == (family, Nn)
+    else:
+        prob = _prob(family, N, Nn)
+    cfg = SamplerConfig(chains=24, warmup=80, samples=60, seed=35, max_treedepth=depth,
+                        precision="mixed" if variant == "mixed" else "f64")
     for pair in (None, "1"):
         info, a = _run_env(prob, cfg, FITOCT_NO_BIDI=None, FITOCT_NO_PAIR=pair, FITOCT_NO_SPEC=None)
         info0, b = _run_env(prob, cfg, FITOCT_NO_BIDI="1", FITOCT_NO_PAIR=None, FITOCT_NO_SPEC=None)
+        assert variant is None or info["basis_mode"] == 1   # mixed / caller's B: row mode
         assert info["chains_per_tile"] == 1 and info["sampler"] == 2
         assert info["two_ended"] == 1 and info0["two_ended"] == 0 and info0["ring_records"] == 0
         assert info["ring_records"] == 1 and info["ring_records_in_levels"] == 0
