@@ -4,8 +4,9 @@
 // of every wait (Patience) and the three orderings of a wave's LDS traffic.
 //
 // This header opens namespace fitoct for the whole translation unit: the layers after it
-// (dev_global.h ... gradient_pass.h) and the rest of nuts_device.hip, which includes them
-// in order, are written inside it; nuts_device.hip closes it at its end.
+// (dev_global.h ... gradient_pass.h, then chain.h, tile_migrate.h, nuts_kernel.h) and the
+// rest of nuts_device.hip, which includes them in order, are written inside it;
+// nuts_device.hip closes it at its end.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -110,6 +111,12 @@ constexpr int BD_GEN_MASK = (1 << 15) - 1;
 // BD_GEN | BD_ENDED: a migrating tile's chain has booked transition BD_GEN's tree to its end
 // (its producers stop, and wait for the next transition or the launch's end)
 constexpr int BD_ENDED = 1 << 20;
+// (gen << 16) | v, the hand-off words that carry their transition.  Shifted unsigned: a paired
+// tile's bridge forms it from BD_GEN | BD_ENDED too, whose bit 20 a signed shift would push
+// past int's sign bit (undefined before C++20).  Same bits; the generation is not masked.
+__device__ __forceinline__ int gen_word(int gen, int v) {
+  return (int)(((unsigned)gen << 16) | (unsigned)v);
+}
 // a producer runs at most this many doublings past the booked one (lookahead 1 / 2 / 5
 // measured -1.0 / -0.2 / +-0 % on config 2, profiles/r05_ab_stage.txt)
 constexpr int BIDI_LOOK = 3;

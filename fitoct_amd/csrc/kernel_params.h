@@ -22,7 +22,7 @@ constexpr int POOL_VECS = 2;      // vectors per proposal-pool slot in HBM (q, g
 constexpr int KMAX = 24;          // max GP control points (K^-1 tile in LDS)
 constexpr int NSTAMP = 108;        // diagnostic stamps per tile (FITOCT_STAMPS)
 // Layout of a tile's NSTAMP stamps: written by the profiling build's kernels
-// (nuts_device.hip, kProfile), read by the report (stamps_report.cpp).  Cycles are
+// (dev_common.h kProfile), read by the report (stamps_report.cpp).  Cycles are
 // s_memtime, "rt" the 100 MHz s_memrealtime; a range's length is in brackets.
 enum StampSlot : int {
   SS_SWEEPS = 0,          // sweeps of the tile (gradient wave 0)
@@ -146,7 +146,7 @@ struct KParams {
   int* mig;                 // MigCtrl header | load | free_mask | mailbox (see MigCtrl)
   double* mig_img;          // [tiles * GMAX][mig_img_words] chain images in flight
   int mig_tiles, mig_img_words;
-  int spec;                 // 1: the speculative-leaf sampler (nuts_device.hip leaf_spec)
+  int spec;                 // 1: the speculative-leaf sampler (chain.h leaf_spec)
   int spec_live;            // ... a chain speculates while its tile hosts <= spec_live live
                             // chains (tiles of one chain: always, with a helper wave)
   // ---- run-time progress / cancellation (host-pinned; nullptr: off) ----
@@ -162,7 +162,7 @@ struct KParams {
   // ---- two-ended trajectories (tiles of one chain; 0: off) ----
   // two producer waves build the subtrees of the trajectory's backward and forward ends from
   // the transition's start at once, each in its own chain area; the chain's wave books the
-  // trajectory level from one record per subtree (nuts_device.hip, "two-ended trajectories")
+  // trajectory level from one record per subtree (chain.h, "two-ended trajectories")
   int bidi;                 // 1: on (the tile's LDS then carves 3 chain areas)
   // ---- two-ended trajectories in a migrating launch's tail (0: off) ----
   // once at most tail_left chains of the launch are unfinished, a chain alone in its tile
@@ -175,7 +175,7 @@ struct KParams {
   unsigned long long* bidi_count;   // two-ended transitions of the launch (fitoct_result)
   // ---- paired tiles (one-chain tiles with two-ended trajectories, 2 x tiles <= CUs; 0: off) ----
   // the forward end of each tile's trajectories grows in a partner tile with its own gradient
-  // waves (nuts_device.hip "paired tiles"); the grid is 16 * ceil(pair_tiles / 8) blocks
+  // waves (nuts_kernel.h "paired tiles"); the grid is 16 * ceil(pair_tiles / 8) blocks
   int pair;
   int pair_tiles;           // tiles of the launch (the tile map's entries)
   int pair_stride;          // doubles per pair in pair_buf: start (4 vectors + 8) | 2 records (5 + 16)

@@ -40,7 +40,7 @@ struct DeviceError {
 };
 
 // theta = theta0, lambda at its prior mean (normal family), everything else 0:
-// the centre of the sampler's initialisation (nuts_device.hip act_init_start)
+// the centre of the sampler's initialisation (chain.h act_init_start)
 void default_init(const fitoct_problem* p, Vec& q) {
   const int D = model_dim(p->prior_type, p->Nn);
   q.assign(D, 0.0);

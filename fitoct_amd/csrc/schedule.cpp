@@ -46,7 +46,7 @@ constexpr int kSpecLiveMigrating = 3;
 // (the kernel's static LDS comes on top of the carve: STATIC_LDS_RESERVE)
 constexpr int kLdsBudget = 160 * 1024 - STATIC_LDS_RESERVE;
 
-// Paired tiles (nuts_device.hip "paired tiles"): a launch of one-chain tiles with two-ended
+// Paired tiles (nuts_kernel.h "paired tiles"): a launch of one-chain tiles with two-ended
 // trajectories whose 2 x tiles (in whole groups of 8 + 8 blocks) fit on the chip grows each
 // trajectory's forward end in a partner tile with its own gradient waves, instead of sharing
 // the tile's.  Same draws bit for bit: the partner runs the same producer on the same values.
@@ -81,7 +81,7 @@ Schedule choose_schedule(int ppl, int mode, int chains, int batch_chains, int nc
   // keeps a pending tile off the chip; off in batch mode (a tile holds one
   // problem's bins) and with FITOCT_NO_MIGRATE.
   s.migrate = batch_chains == 0 && G >= 2 && s.tiles <= ncu && !sw.no_migrate;
-  // Speculative leaves (nuts_device.hip leaf_spec).  A tile of one (two) chain(s) always
+  // Speculative leaves (chain.h leaf_spec).  A tile of one (two) chain(s) always
   // speculates, with a spare NUTS wave helping each chain (config 2 +4 %).  A tile of several chains
   // has no spare wave: while it hosts 4 live chains the sweep hides the sampler's latency
   // and speculation only adds work, so a migrating chain speculates only once its tile has
@@ -99,7 +99,7 @@ Schedule choose_schedule(int ppl, int mode, int chains, int batch_chains, int nc
     s.spec_live = std::max(0, std::min(live, GMAX));
     s.spec = s.spec_live > 0 ? 1 : 0;
   }
-  // Two-ended trajectories (nuts_device.hip): tiles of one chain grow the trajectory's two
+  // Two-ended trajectories (chain.h): tiles of one chain grow the trajectory's two
   // ends at once -- two spare NUTS waves build the subtrees of each direction whole, each in a
   // chain area of its own, and the chain's wave books the trajectory level from one record per
   // subtree.  Same draws bit for bit.  The three chain areas must fit, else the tile stays on
@@ -112,7 +112,7 @@ Schedule choose_schedule(int ppl, int mode, int chains, int batch_chains, int nc
       s.lds = base;
     }
   }
-  // Two-ended trajectories in the tail of a migrating launch (nuts_device.hip receive_chain):
+  // Two-ended trajectories in the tail of a migrating launch (tile_migrate.h receive_chain):
   // the producers are idle receivers of the tile (their own chain areas: no LDS added).  Same
   // draws bit for bit.  FITOCT_NO_TAIL_BIDI=1: off; FITOCT_TAIL_LEFT=n: start at n unfinished
   // chains (default: every chain of the launch -- a chain alone in its tile goes two-ended

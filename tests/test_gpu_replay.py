@@ -18,45 +18,25 @@ transitions after a metric update, the sampling phase, and any fault the sampler
 The shapes are tests/replay_cases.py's; the measured figures are in DESIGN.md (parity notes)."""
 from __future__ import annotations
 
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
 import replay_audit as RA
 import replay_cases as RC
-from fitoct_amd import Batch, Plan
+from fitoct_amd import Batch
+from planner_env import plan_run, switches
 
 pytestmark = pytest.mark.gpu
 
 NTHREADS = 16
-SWITCHES = ("FITOCT_NO_GEO", "FITOCT_NO_PAIR", "FITOCT_PAIR", "FITOCT_NO_MIGRATE", "FITOCT_NO_SPEC",
-            "FITOCT_NO_BIDI", "FITOCT_NO_TAIL_BIDI", "FITOCT_SPEC", "FITOCT_SPEC_LIVE",
-            "FITOCT_TAIL_LEFT")
 SPECULATIVE, MIGRATE_SPEC = 2, 3      # FITOCT_SAMPLER_*
 POLY, ROWS = 0, 1                     # fitoct_plan_info::basis_mode
 
 
-@contextlib.contextmanager
-def _switches(**env):
-    """The planner's defaults (no environment switch set) but for ``env``."""
-    old = {k: os.environ.pop(k, None) for k in SWITCHES}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k in SWITCHES:
-            os.environ.pop(k, None)
-            if old[k] is not None:
-                os.environ[k] = old[k]
-
-
 def _launch(case, prob, **env):
     cfg = case.cfg()
-    with _switches(**env), Plan(prob, cfg) as pl:
-        pl.run()
-        return pl.info, cfg, pl.download()
+    info, out = plan_run(prob, cfg, **env)
+    return info, cfg, out
 
 
 def _check(name, prob, cfg, out, chains=None, replay=True):
@@ -110,7 +90,7 @@ def test_batch_of_files():
     case = RC.REPLAY["batch"]
     probs = case.make()
     cfg = case.cfg()
-    with _switches(), Batch(probs, cfg) as b:
+    with switches(), Batch(probs, cfg) as b:
         b.run()
         info, outs = b.info, [b.download(p) for p in range(len(probs))]
     assert info["chains_per_tile"] == 1 and info["sampler"] == SPECULATIVE

@@ -1,4 +1,4 @@
-"""Speculative leaves (nuts_device.hip leaf_spec / act_spec_book and the helper wave):
+"""Speculative leaves (chain.h leaf_spec / act_spec_book, nuts_kernel.h's helper wave):
 with one chain per tile the next leapfrog position is swept while the current leaf's
 merges and U-turn checks run, and a helper wave computes its prior part.  The draws
 must equal the plain sampler's (FITOCT_NO_SPEC=1) bit for bit, trajectory ends
@@ -7,29 +7,14 @@ several chains, migrating or not, where there is no helper wave and a chain spec
 only while its tile has thinned out (or at every leaf with FITOCT_SPEC=1)."""
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import pytest
 
 from fitoct_amd import Plan, SamplerConfig
+from planner_env import plan_run, switches
 from test_gpu_sampler import _prob
 
 pytestmark = pytest.mark.gpu
-
-
-def _run(prob, cfg, spec):
-    old = os.environ.pop("FITOCT_NO_SPEC", None)
-    if not spec:
-        os.environ["FITOCT_NO_SPEC"] = "1"
-    try:
-        with Plan(prob, cfg) as pl:
-            pl.run()
-            return pl.info, pl.download()
-    finally:
-        os.environ.pop("FITOCT_NO_SPEC", None)
-        if old is not None:
-            os.environ["FITOCT_NO_SPEC"] = old
 
 
 @pytest.mark.parametrize("family,N,depth", [("normal", 512, 10), ("lasso", 300, 8),
@@ -37,33 +22,14 @@ def _run(prob, cfg, spec):
 def test_speculative_leaves_preserve_draws_bitwise(family, N, depth):
     prob = _prob(family, N, 15)
     cfg = SamplerConfig(chains=24, warmup=80, samples=60, seed=33, max_treedepth=depth)
-    info, a = _run(prob, cfg, spec=True)
-    info0, b = _run(prob, cfg, spec=False)
+    info, a = plan_run(prob, cfg)
+    info0, b = plan_run(prob, cfg, FITOCT_NO_SPEC="1")
     assert info["chains_per_tile"] == 1
     assert info["sampler"] == 2 and info0["sampler"] == 0   # FITOCT_SAMPLER_SPECULATIVE / _PLAIN
     np.testing.assert_array_equal(a.draws, b.draws)
     np.testing.assert_array_equal(a.stepsize, b.stepsize)
     np.testing.assert_array_equal(a.inv_metric, b.inv_metric)
     assert a.total_leapfrogs == b.total_leapfrogs
-
-
-def _run_env(prob, cfg, **env):
-    old = {k: os.environ.get(k) for k in env}
-    try:
-        for k, v in env.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-        with Plan(prob, cfg) as pl:
-            pl.run()
-            return pl.info, pl.download()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.mark.parametrize("live", [None, "4"])
@@ -74,8 +40,8 @@ def test_migrating_plans_speculate_in_the_tail_bitwise(live):
     metrics and leapfrog counts as the plain migrating sampler."""
     prob = _prob("horseshoe", 2048, 15)
     cfg = SamplerConfig(chains=1024, warmup=60, samples=40, seed=3, max_treedepth=7)
-    info, a = _run_env(prob, cfg, FITOCT_SPEC_LIVE=live, FITOCT_NO_SPEC=None)
-    info0, b = _run_env(prob, cfg, FITOCT_SPEC_LIVE=None, FITOCT_NO_SPEC="1")
+    info, a = plan_run(prob, cfg, FITOCT_SPEC_LIVE=live)
+    info0, b = plan_run(prob, cfg, FITOCT_NO_SPEC="1")
     assert info["chains_per_tile"] == 4 and info["sampler"] == 3   # MIGRATE_SPEC
     assert info0["sampler"] == 1                                   # MIGRATE
     np.testing.assert_array_equal(a.draws, b.draws)
@@ -91,18 +57,8 @@ def test_tiles_of_several_chains_speculate_without_helper_bitwise():
     part itself (not the default: it is slower there).  Same draws as the plain sampler."""
     prob = _prob("horseshoe", 512, 15)
     cfg = SamplerConfig(chains=1024, warmup=40, samples=30, seed=5, max_treedepth=7)
-    old = {k: os.environ.get(k) for k in ("FITOCT_NO_MIGRATE", "FITOCT_SPEC")}
-    os.environ["FITOCT_NO_MIGRATE"] = "1"
-    os.environ["FITOCT_SPEC"] = "1"
-    try:
-        info, a = _run(prob, cfg, spec=True)
-        info0, b = _run(prob, cfg, spec=False)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
+    info, a = plan_run(prob, cfg, FITOCT_NO_MIGRATE="1", FITOCT_SPEC="1")
+    info0, b = plan_run(prob, cfg, FITOCT_NO_MIGRATE="1", FITOCT_SPEC="1", FITOCT_NO_SPEC="1")
     assert info["chains_per_tile"] == 4
     assert info["sampler"] == 2 and info0["sampler"] == 0
     np.testing.assert_array_equal(a.draws, b.draws)
@@ -115,18 +71,10 @@ def test_batch_speculates_bitwise():
     from fitoct_amd import sample_batch
     probs = [_prob("normal", 481, 15, seed=40 + f) for f in range(6)]
     cfg = SamplerConfig(chains=4, warmup=40, samples=30, seed=9)
-    old = {k: os.environ.pop(k, None) for k in ("FITOCT_NO_SPEC", "FITOCT_SPEC")}
-    try:
-        os.environ["FITOCT_SPEC"] = "1"
+    with switches(FITOCT_SPEC="1"):
         a = sample_batch(probs, cfg)
-        os.environ.pop("FITOCT_SPEC")
-        os.environ["FITOCT_NO_SPEC"] = "1"
+    with switches(FITOCT_NO_SPEC="1"):
         b = sample_batch(probs, cfg)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
     for x, y in zip(a, b):
         np.testing.assert_array_equal(x.draws, y.draws)
 
@@ -160,7 +108,7 @@ def test_two_ended_trajectories_preserve_draws_bitwise(family, N, Nn, depth, var
     """Tiles of one chain grow both ends of each trajectory at once: two producer waves build
     the subtrees of each direction whole (weights, merges, U-turn checks, proposal) in chain
     areas of their own and hand the chain's wave one record per subtree, which it books at the
-    trajectory level in Stan's tree order (nuts_device.hip "two-ended trajectories").  Same
+    trajectory level in Stan's tree order (chain.h "two-ended trajectories").  Same
     draws, step sizes, metrics and leapfrog counts as the one-ended deep-speculation path
     (FITOCT_NO_BIDI=1), with trees cut at max_treedepth 4 and the ppl = 2 carve (Nn = 20),
     in mixed precision and with a caller-supplied basis (test_gpu_logp's non-SE B).
@@ -175,8 +123,8 @@ def test_two_ended_trajectories_preserve_draws_bitwise(family, N, Nn, depth, var
     cfg = SamplerConfig(chains=24, warmup=80, samples=60, seed=35, max_treedepth=depth,
                         precision="mixed" if variant == "mixed" else "f64")
     for pair in (None, "1"):
-        info, a = _run_env(prob, cfg, FITOCT_NO_BIDI=None, FITOCT_NO_PAIR=pair, FITOCT_NO_SPEC=None)
-        info0, b = _run_env(prob, cfg, FITOCT_NO_BIDI="1", FITOCT_NO_PAIR=None, FITOCT_NO_SPEC=None)
+        info, a = plan_run(prob, cfg, FITOCT_NO_PAIR=pair)
+        info0, b = plan_run(prob, cfg, FITOCT_NO_BIDI="1")
         assert variant is None or info["basis_mode"] == 1   # mixed / caller's B: row mode
         assert info["chains_per_tile"] == 1 and info["sampler"] == 2
         assert info["two_ended"] == 1 and info0["two_ended"] == 0 and info0["ring_records"] == 0
@@ -197,10 +145,10 @@ def test_two_ended_off_where_three_chain_areas_do_not_fit():
     usual 4 chains run and match the plain sampler bit for bit."""
     prob = _prob("normal", 512, 20)
     cfg = SamplerConfig(chains=4, warmup=60, samples=40, seed=21, max_treedepth=10)
-    info, a = _run_env(prob, cfg, FITOCT_NO_BIDI=None, FITOCT_NO_SPEC=None)
+    info, a = plan_run(prob, cfg)
     assert info["chains_per_tile"] == 1 and info["two_ended"] == 0
     assert info["lds_bytes"] <= 160 * 1024
-    _, b = _run_env(prob, cfg, FITOCT_NO_BIDI=None, FITOCT_NO_SPEC="1")
+    _, b = plan_run(prob, cfg, FITOCT_NO_SPEC="1")
     np.testing.assert_array_equal(a.draws, b.draws)
     assert np.all(np.isfinite(a.draws[:, :, 0]))
 
@@ -211,16 +159,10 @@ def test_batch_of_one_chain_tiles_two_ended_bitwise():
     from fitoct_amd import sample_batch
     probs = [_prob("normal", 481, 15, seed=60 + f) for f in range(5)]
     cfg = SamplerConfig(chains=4, warmup=40, samples=30, seed=11)
-    old = {k: os.environ.pop(k, None) for k in ("FITOCT_NO_SPEC", "FITOCT_SPEC", "FITOCT_NO_BIDI")}
-    try:
+    with switches():
         a = sample_batch(probs, cfg)
-        os.environ["FITOCT_NO_BIDI"] = "1"
+    with switches(FITOCT_NO_BIDI="1"):
         b = sample_batch(probs, cfg)
-    finally:
-        for k, v in old.items():
-            os.environ.pop(k, None)
-            if v is not None:
-                os.environ[k] = v
     for x, y in zip(a, b):
         np.testing.assert_array_equal(x.draws, y.draws)
 
@@ -238,21 +180,9 @@ def test_two_chain_tiles_deep_speculation_bitwise(files, chains, env):
     cfg = SamplerConfig(chains=chains, warmup=40, samples=30, seed=13)
     outs = {}
     for spec in (True, False):
-        old = {k: os.environ.get(k) for k in ("FITOCT_NO_SPEC", "FITOCT_SPEC", *env)}
-        try:
-            for k in old:
-                os.environ.pop(k, None)
-            os.environ.update(env)
-            if not spec:
-                os.environ["FITOCT_NO_SPEC"] = "1"
-            with Batch(probs, cfg) as b:
-                b.run()
-                outs[spec] = (b.info, [b.download(p) for p in range(files)])
-        finally:
-            for k, v in old.items():
-                os.environ.pop(k, None)
-                if v is not None:
-                    os.environ[k] = v
+        with switches(**env, FITOCT_NO_SPEC=None if spec else "1"), Batch(probs, cfg) as b:
+            b.run()
+            outs[spec] = (b.info, [b.download(p) for p in range(files)])
     (ia, a), (ib, b) = outs[True], outs[False]
     assert ia["chains_per_tile"] == 2 and ia["sampler"] == 2 and ib["sampler"] == 0
     assert ia["lds_bytes"] <= 160 * 1024

@@ -114,6 +114,18 @@ def test_schedule_table(what, shape, switches, want):
         assert s["grid"] == s["tiles"]
 
 
+def test_planner_env_lists_every_switch_the_planner_reads():
+    """The GPU variant tests run "the planner's defaults but for ..." by clearing
+    planner_env.SWITCHES: every name Switches::from_env passes to getenv (directly or through
+    its ``set`` lambda) must be in it, or a new switch leaks into those comparisons."""
+    import planner_env
+    with open(os.path.join(ROOT, "fitoct_amd", "csrc", "schedule.cpp")) as f:
+        read = re.findall(r'\b(?:getenv|set)\("(\w+)"\)', f.read())
+    assert len(read) >= 12 and len(set(read)) == len(read)
+    assert set(read) == set(planner_env.SWITCHES)
+    assert planner_env.SWITCHES == tuple("FITOCT_" + k.upper() for k in SWITCHES)
+
+
 def test_two_ended_tiles_carve_three_chain_areas():
     """config 2: lds = lds_bytes(1, 3, 10), the carve of a tile of three chains (768 chains);
     one-ended (no_bidi) it is the one-chain carve, which is smaller."""
