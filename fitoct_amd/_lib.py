@@ -115,6 +115,15 @@ class VbResult(C.Structure):
     ]
 
 
+class SummaryConfig(C.Structure):
+    _fields_ = [
+        ("first_iter", C.c_int32), ("n_probs", C.c_int32), ("probs", C.c_double * 16),
+        ("max_staging_bytes", C.c_int64), ("device", C.c_int32),
+    ]
+
+
+MAX_PROBS = 16   # include/fitoct.h fitoct_summary_config.probs
+
 TERMINATION = {0: "success", 10: "absolute parameter change", 20: "absolute objective change",
                21: "relative objective change", 30: "gradient norm", 31: "relative gradient",
                40: "maximum iterations", -1: "line search failed"}
@@ -179,6 +188,15 @@ SIGNATURES = [
      [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     ("fitoct_split_rhat_ess", C.c_int32, [_dp, C.c_int32, C.c_int32, _dp, _dp]),
     ("fitoct_rank_rhat", C.c_int32, [_dp, C.c_int32, C.c_int32, _dp]),
+    ("fitoct_default_summary_config", None, [C.POINTER(SummaryConfig)]),
+    ("fitoct_summary_width", C.c_int32, [C.c_int32]),
+    ("fitoct_summary_device", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SummaryConfig),
+      C.c_void_p, _dp]),
+    ("fitoct_summary_host", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_plan_summary", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_batch_summary", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
 ]
 
 _LIB = None

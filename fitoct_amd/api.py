@@ -182,6 +182,96 @@ def logp_grad(prob: ExpGPProblem, q: np.ndarray, precision: str = "f64", device:
     return lp, g, s2
 
 
+DEFAULT_PROBS = (0.025, 0.25, 0.5, 0.75, 0.975)   # rstan::summary's probs
+
+
+def _summary_config(first_iter, probs, max_staging_bytes=0, device=0) -> _lib.SummaryConfig:
+    probs = tuple(float(p) for p in probs)
+    if len(probs) > _lib.MAX_PROBS:
+        raise ValueError(f"at most {_lib.MAX_PROBS} probabilities per summary")
+    c = _lib.SummaryConfig()
+    lib().fitoct_default_summary_config(C.byref(c))
+    c.first_iter = int(first_iter)
+    c.n_probs = len(probs)
+    for i, p in enumerate(probs):
+        c.probs[i] = p
+    c.max_staging_bytes = int(max_staging_bytes)
+    c.device = int(device)
+    return c
+
+
+def _problem_array(prob):
+    probs = [prob] if isinstance(prob, ExpGPProblem) else list(prob)
+    if not probs:
+        raise ValueError("a summary needs at least one problem")
+    arr = (_lib.Problem * len(probs))()
+    for i, p in enumerate(probs):
+        arr[i] = p.to_c()
+    return probs, arr   # probs keeps the numpy buffers behind arr alive
+
+
+def summary_rows(table: np.ndarray, prob: ExpGPProblem, probs=DEFAULT_PROBS, pars=None) -> dict:
+    """One group's summary table ``[P, 5 + len(probs)]`` (``fitoct_summary_*``) as the dict
+    :meth:`fitoct_amd.stanfit.StanFit.summary` returns: ``{name: {"mean", "se_mean", "sd",
+    "2.5%", ..., "n_eff", "Rhat"}}``, all-NaN rows omitted, ``pars`` selecting names or base
+    names (``"theta"`` -> ``theta.1`` ...) as in rstan."""
+    from .stanfit import _base, output_columns
+    names = output_columns(prob)
+    if pars is None:
+        sel = list(range(len(names)))
+    else:
+        sel = []
+        for p in ([pars] if isinstance(pars, str) else pars):
+            hit = [i for i, c in enumerate(names) if c == p or _base(c) == p]
+            if not hit:
+                raise KeyError(f"no parameter {p!r} in the fit")
+            sel += hit
+    keys = ["mean", "se_mean", "sd"] + [f"{100 * p:g}%" for p in probs] + ["n_eff", "Rhat"]
+    rows = {}
+    for i in sel:
+        if np.all(np.isnan(table[i])):
+            continue
+        rows[names[i]] = {k: float(v) for k, v in zip(keys, table[i])}
+    return rows
+
+
+def summary_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter: int = 0,
+                   probs=DEFAULT_PROBS, max_staging_bytes: int = 0, device: int = 0,
+                   stream: int = 0) -> np.ndarray:
+    """Posterior summary of draws that lie in device memory (``fitoct_summary_device``):
+    ``d_draws`` is the device pointer (e.g. a gathered torch tensor's ``data_ptr()``) of raw
+    sampler draws ``[groups][chains][iters_saved][n_cols]``, ``prob`` one problem or one per
+    group.  Returns ``[groups, P, 5 + len(probs)]`` (rows: :func:`summary_rows`)."""
+    ps, arr = _problem_array(prob)
+    c = _summary_config(first_iter, probs, max_staging_bytes, device)
+    width = 5 + c.n_probs
+    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
+    out = np.empty((len(ps), max(n_out, 0), width))
+    check(lib().fitoct_summary_device(arr, len(ps), int(chains), int(iters_saved),
+                                      C.c_void_p(d_draws or None), C.byref(c),
+                                      C.c_void_p(stream or None), dptr(out)))
+    return out
+
+
+def summary_host(draws: np.ndarray, prob, first_iter: int = 0, probs=DEFAULT_PROBS) -> np.ndarray:
+    """The same table computed on the host (``fitoct_summary_host``) from raw draws
+    ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
+    ps, arr = _problem_array(prob)
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    if draws.ndim == 3:
+        draws = draws[None]
+    if draws.ndim != 4 or draws.shape[0] != len(ps):
+        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
+    if draws.shape[3] != ps[0].D + 8:
+        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    c = _summary_config(first_iter, probs)
+    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
+    out = np.empty((len(ps), max(n_out, 0), 5 + c.n_probs))
+    check(lib().fitoct_summary_host(arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws),
+                                    C.byref(c), dptr(out)))
+    return out
+
+
 @dataclass
 class SampleOutput:
     draws: np.ndarray          # [chains, iters_saved, n_cols]
@@ -303,6 +393,20 @@ class Plan:
                             self.cfg.chain_offset, int(r.migrations), self.cfg,
                             int(r.two_ended_transitions), int(r.paired_transitions))
 
+    def summary(self, pars=None, probs=DEFAULT_PROBS, first_iter=None,
+                max_staging_bytes: int = 0) -> dict:
+        """``rstan::summary(fit, pars)$summary`` of the last run, computed on the device from
+        the draws where they lie (the plan's buffer or the ``d_draws`` of the run; nothing is
+        downloaded but the table): the dict of :meth:`fitoct_amd.stanfit.StanFit.summary`.
+        ``first_iter`` (saved iterations to skip) defaults to the saved warmup."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        c = _summary_config(first_iter, probs, max_staging_bytes)
+        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._p))
+        out = np.empty((n_out, 5 + c.n_probs))
+        check(lib().fitoct_plan_summary(self._h, C.byref(c), dptr(out)))
+        return summary_rows(out, self.prob, probs, pars)
+
     def close(self):
         if getattr(self, "_h", None):
             lib().fitoct_plan_destroy(self._h)
@@ -371,6 +475,20 @@ class Batch:
                             dataclasses.replace(self.cfg,
                                                 chain_offset=self.cfg.chain_offset + problem * C_),
                             int(r.two_ended_transitions), int(r.paired_transitions))
+
+    def summary(self, problem=None, pars=None, probs=DEFAULT_PROBS, first_iter=None,
+                max_staging_bytes: int = 0):
+        """Device summary of the last run (:meth:`Plan.summary`) of every file in one call: a
+        list with one dict per problem, or problem ``problem``'s dict."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        c = _summary_config(first_iter, probs, max_staging_bytes)
+        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._arr[0]))
+        out = np.empty((len(self.probs), n_out, 5 + c.n_probs))
+        check(lib().fitoct_batch_summary(self._h, C.byref(c), dptr(out)))
+        if problem is not None:
+            return summary_rows(out[problem], self.probs[problem], probs, pars)
+        return [summary_rows(out[p], self.probs[p], probs, pars) for p in range(len(self.probs))]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -44,6 +44,8 @@ SOURCES = [
     ("nuts_lasso", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=1"]),
     ("nuts_horseshoe", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=2"]),
     ("nuts_monoexp", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=3"]),
+    # the posterior summary's kernels and entry points (no family parameter)
+    ("summary_device", "summary_device.hip", "hipcc", _KERNEL),
     ("fitoct_api", "fitoct_api.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("multi_device", "multi_device.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("host_model", "host_model.cpp", "g++", ["-O2", "-std=c++17"]),
@@ -52,6 +54,8 @@ SOURCES = [
     ("schedule", "schedule.cpp", "g++", ["-O2", "-std=c++17"]),
     ("stamps_report", "stamps_report.cpp", "g++", ["-O2", "-std=c++17"]),
 ]
+# objects whose kernels' resource remarks are kept beside them (<object>.resources.txt)
+RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["summary_device"]
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")
@@ -134,7 +138,7 @@ def build(force: bool = False, verbose: bool = False, sanitize: bool = False) ->
                "-I/opt/rocm/include", "-c", os.path.join(CSRC, src), "-o", obj]
         if cc != "hipcc":
             cmd.insert(1, "-D__HIP_PLATFORM_AMD__")
-        record = name.startswith("nuts_") and not sanitize
+        record = name in RECORDED and not sanitize
         if record:   # per-kernel VGPR / spill / scratch remarks, kept beside the object
             cmd.append("-Rpass-analysis=kernel-resource-usage")
         r = subprocess.run(cmd, capture_output=True, text=True)

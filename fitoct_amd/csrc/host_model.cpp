@@ -11,6 +11,7 @@
 
 #include "fitoct.h"
 #include "host_internal.h"
+#include "summary_shared.h"
 
 namespace fitoct {
 
@@ -126,17 +127,8 @@ std::string column_name(int prior, int Nn, int i) {
 // --------------------------------------------------------------------------
 // diagnostics (stan::analyze, as printed by rstan::summary)
 // --------------------------------------------------------------------------
-static double mean_of(const double* x, int n) {
-  double s = 0.0;
-  for (int i = 0; i < n; ++i) s += x[i];
-  return s / n;
-}
-static double var_of(const double* x, int n) {  // sample variance (n-1)
-  const double m = mean_of(x, n);
-  double s = 0.0;
-  for (int i = 0; i < n; ++i) s += (x[i] - m) * (x[i] - m);
-  return s / (n - 1);
-}
+// (mean_of, var_of, the potential scale reduction and Geyer's rule live in summary_shared.h:
+// the device summary applies the same functions to moments reduced on the GPU)
 
 // potential scale reduction on already-split chains c[m][n]
 static double psr(const std::vector<const double*>& c, int n) {
@@ -146,9 +138,7 @@ static double psr(const std::vector<const double*>& c, int n) {
     cm[j] = mean_of(c[j], n);
     cv[j] = var_of(c[j], n);
   }
-  const double B = n * var_of(cm.data(), m);
-  const double W = mean_of(cv.data(), m);
-  return sqrt((B / W + n - 1) / n);
+  return psr_moments(cm.data(), cv.data(), m, n);
 }
 
 // stan::analyze::compute_effective_sample_size on already-split chains
@@ -170,41 +160,7 @@ static double ess_chains(const std::vector<const double*>& c, int n) {
     }
     return tot / m;
   };
-  const double mean_var = mean_of(cvar.data(), m);
-  double var_plus = mean_var * (n - 1) / n;
-  if (m > 1) var_plus += var_of(cm.data(), m);
-  if (!(var_plus > 0.0)) return NAN;
-  std::vector<double> rho(n + 2, 0.0);
-  double rho_even = 1.0;
-  double rho_odd = 1.0 - (mean_var - acov_mean(1)) / var_plus;
-  rho[0] = 1.0;
-  rho[1] = rho_odd;
-  int t = 1;
-  while (t < n - 4 && (rho_even + rho_odd) > 0.0) {
-    rho_even = 1.0 - (mean_var - acov_mean(t + 1)) / var_plus;
-    rho_odd = 1.0 - (mean_var - acov_mean(t + 2)) / var_plus;
-    if ((rho_even + rho_odd) >= 0.0) {
-      rho[t + 1] = rho_even;
-      rho[t + 2] = rho_odd;
-    }
-    t += 2;
-  }
-  const int max_t = t;
-  if (rho_even > 0.0) rho[max_t + 1] = rho_even;
-  t = 1;
-  while (t <= max_t - 2) {
-    if (rho[t + 1] + rho[t + 2] > rho[t - 1] + rho[t]) {
-      rho[t + 1] = (rho[t - 1] + rho[t]) / 2.0;
-      rho[t + 2] = rho[t + 1];
-    }
-    t += 2;
-  }
-  const double ess = (double)m * n;
-  double tau = -1.0;
-  for (int i = 0; i <= max_t; ++i) tau += 2.0 * rho[i];
-  tau += rho[max_t + 1];
-  tau = std::max(tau, 1.0 / log10(ess));
-  return ess / tau;
+  return ess_moments(cm.data(), cvar.data(), m, n, acov_mean);
 }
 
 int split_rhat_ess(const double* x, int chains, int n, double* rhat, double* ess) {

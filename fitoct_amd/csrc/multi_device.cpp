@@ -54,6 +54,16 @@ int resolve_devices(const fitoct_config* cfg, int units, std::vector<int>& devs)
   return FITOCT_OK;
 }
 
+// the device a caller's d_draws buffer lives on (FITOCT_E_ARG if it is not device memory)
+int buffer_device(const void* p, int& dev) {
+  hipPointerAttribute_t a{};
+  HIP_TRY(hipPointerGetAttributes(&a, p));
+  if (a.type != hipMemoryTypeDevice)
+    return fail(FITOCT_E_ARG, "d_draws must be a device buffer (hipMalloc)");
+  dev = a.device;
+  return FITOCT_OK;
+}
+
 namespace {
 
 // The calling thread's HIP device is restored when a multi-device call returns (the
@@ -100,16 +110,6 @@ int on_devices(int n, F&& f) {
   for (int r = 0; r < n && first < 0; ++r)
     if (rc[r] != FITOCT_OK) first = r;
   return first < 0 ? FITOCT_OK : fail(rc[first], msg[first]);
-}
-
-// the device a caller's d_draws buffer lives on (FITOCT_E_ARG if it is not device memory)
-int buffer_device(const void* p, int& dev) {
-  hipPointerAttribute_t a{};
-  HIP_TRY(hipPointerGetAttributes(&a, p));
-  if (a.type != hipMemoryTypeDevice)
-    return fail(FITOCT_E_ARG, "d_draws must be a device buffer (hipMalloc)");
-  dev = a.device;
-  return FITOCT_OK;
 }
 
 // FITOCT_GATHER_COPY=1 (tests): blocks on the buffer's own device are also written to a
@@ -530,6 +530,8 @@ int group_batch_run(fitoct_batch* b, void* d_draws, void* stream) {
   b->kernel_ms = 0.0;
   for (const fitoct_batch* sb : b->subs) b->kernel_ms = std::max(b->kernel_ms, sb->kernel_ms);
   b->ran = (rc == FITOCT_OK);
+  b->gather_dst = d_draws;   // where fitoct_batch_summary finds the gathered draws
+  b->gather_dev = gdev;
   return rc;
 }
 

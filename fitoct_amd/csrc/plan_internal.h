@@ -105,6 +105,8 @@ struct fitoct_batch {
   std::vector<int> sub_off;
   int n_problems = 0;
   hipStream_t own_stream = nullptr;   // a sub-batch's own non-blocking stream
+  void* gather_dst = nullptr;  // caller's d_draws of the last multi-device run (or NULL)
+  int gather_dev = -1;         // device holding gather_dst
 };
 
 namespace fitoct {
@@ -112,6 +114,8 @@ namespace fitoct {
 // the device list of a call: ordinals of the first min(n_devices, units) entries of
 // cfg->devices (or {cfg->device} when n_devices == 0); FITOCT_E_ARG on a bad list
 int resolve_devices(const fitoct_config* cfg, int units, std::vector<int>& devs);
+// the device a caller's d_draws buffer lives on (FITOCT_E_ARG if it is not device memory)
+int buffer_device(const void* p, int& dev);
 // contiguous block partition of `total` units over `n` parts (part r: [off, off + cnt))
 void block_range(int total, int n, int r, int& off, int& cnt);
 

@@ -18,65 +18,48 @@
 
 #include "fitoct.h"
 #include "host_internal.h"
+#include "summary_shared.h"
 
 namespace fitoct {
 namespace {
 
-// One output parameter column: where its value comes from.
-enum Src { S_RAW = 0, S_LAMBDA_DATA, S_TAU, S_HS_LAMBDA, S_HS_YGP };
+// One output parameter column: its name and where its value comes from (summary_shared.h,
+// the one copy of the layout and of the transform, shared with the device summary).
 struct OutCol {
   std::string name;
-  int src;
-  int k;   // S_RAW: raw parameter index (0..D, D = br); S_HS_*: control point
+  OutSpec spec;
 };
+
+OutModel out_model(const fitoct_problem* p) {
+  return {p->prior_type, p->Nn, model_dim(p->prior_type, p->Nn), p->prior_PD, p->lambda_scale};
+}
 
 // Output parameter layout after the leading columns (Stan's order: parameters,
 // transformed parameters, generated quantities).
 std::vector<OutCol> out_layout(const fitoct_problem* p) {
   std::vector<OutCol> v;
-  const int fam = p->prior_type, Nn = p->Nn, D = model_dim(fam, Nn);
+  const OutModel m = out_model(p);
   char b[64];
-  for (int j = 0; j < D; ++j) v.push_back({column_name(fam, Nn, 7 + j), S_RAW, j});
-  if (fam == FITOCT_PRIOR_LASSO) {
-    // ⚑ lassoPrior.stan has no lambda parameter: its penalty lambda_s is data
-    // (lassoPrior.stan:4).  It is exposed as the constant column `lambda` so that
-    // the consumers' pars list resolves (plotExpGP.R:41); rstan reports Rhat NaN for it.
-    v.push_back({"lambda", S_LAMBDA_DATA, 0});
-  } else if (fam == FITOCT_PRIOR_HORSESHOE) {
-    // transformed parameters of horseShoePrior.stan:25-33, in declaration order
-    v.push_back({"tau", S_TAU, 0});
-    for (int k = 0; k < Nn; ++k) {
-      snprintf(b, sizeof b, "lambda.%d", k + 1);
-      v.push_back({b, S_HS_LAMBDA, k});
-    }
-    for (int k = 0; k < Nn; ++k) {
-      snprintf(b, sizeof b, "yGP.%d", k + 1);
-      v.push_back({b, S_HS_YGP, k});
+  for (int i = 0, n = out_n_params(m); i < n; ++i) {
+    const OutSpec c = out_spec(m, i);
+    switch (c.src) {
+      case S_RAW:
+        v.push_back({c.k < m.D ? column_name(m.fam, m.Nn, 7 + c.k) : "br", c});
+        break;
+      case S_LAMBDA_DATA: v.push_back({"lambda", c}); break;   // rstan reports Rhat NaN for it
+      case S_TAU: v.push_back({"tau", c}); break;
+      default:
+        snprintf(b, sizeof b, c.src == S_HS_LAMBDA ? "lambda.%d" : "yGP.%d", c.k + 1);
+        v.push_back({b, c});
     }
   }
-  if (!p->prior_PD) v.push_back({"br", S_RAW, D});   // plotExpGP.R:42-43: no br in a prior run
   return v;
 }
 
 // constrained raw parameters r[0..D-1], br r[D]  ->  output values
 void fill_row(const fitoct_problem* p, const std::vector<OutCol>& lay, const double* r, double* o) {
-  const int Nn = p->Nn;
-  const bool hs = p->prior_type == FITOCT_PRIOR_HORSESHOE;
-  // horseshoe raw order: theta[3] z[Nn] r1_global r2_global r1_local[Nn] r2_local[Nn] sigma
-  const double* z = r + 3;
-  const double* r1l = r + 5 + Nn;
-  const double* r2l = r + 5 + 2 * Nn;
-  const double tau = hs ? r[3 + Nn] * sqrt(r[4 + Nn]) : 0.0;
-  for (size_t i = 0; i < lay.size(); ++i) {
-    const OutCol& c = lay[i];
-    switch (c.src) {
-      case S_RAW: o[i] = r[c.k]; break;
-      case S_LAMBDA_DATA: o[i] = p->lambda_scale; break;
-      case S_TAU: o[i] = tau; break;
-      case S_HS_LAMBDA: o[i] = r1l[c.k] * sqrt(r2l[c.k]); break;
-      case S_HS_YGP: o[i] = z[c.k] * (r1l[c.k] * sqrt(r2l[c.k])) * tau; break;
-    }
-  }
+  const OutModel m = out_model(p);
+  for (size_t i = 0; i < lay.size(); ++i) o[i] = out_value(m, lay[i].spec, r);
 }
 
 int check_layout_problem(const fitoct_problem* p) {

@@ -1,0 +1,180 @@
+// Pieces of the posterior summary that the host and the device must compute the same way
+// (include/fitoct.h "posterior summary"): the output-layout transform of
+// stan_output.cpp, the order-preserving key and the type-7 index arithmetic of the quantiles,
+// and Geyer's truncation rule of the effective sample size.  Compiles for the host (g++) and,
+// where marked FITOCT_HD, for the device (hipcc).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "fitoct.h"
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define FITOCT_HD __host__ __device__
+#else
+#define FITOCT_HD
+#endif
+
+namespace fitoct {
+
+// ---- output layout (Stan's order: parameters, transformed parameters, generated
+// quantities; include/fitoct.h "Stan output") -------------------------------------------
+// One output parameter column: where its value comes from.
+enum Src { S_RAW = 0, S_LAMBDA_DATA, S_TAU, S_HS_LAMBDA, S_HS_YGP };
+struct OutSpec {
+  int src;
+  int k;   // S_RAW: raw parameter index (0..D, D = br); S_HS_*: control point
+};
+// what the layout reads of a fitoct_problem
+struct OutModel {
+  int fam, Nn, D, prior_PD;
+  double lambda_scale;
+};
+
+FITOCT_HD inline int out_n_params(const OutModel& m) {
+  int n = m.D;
+  if (m.fam == FITOCT_PRIOR_LASSO) n += 1;
+  else if (m.fam == FITOCT_PRIOR_HORSESHOE) n += 1 + 2 * m.Nn;
+  return n + (m.prior_PD ? 0 : 1);
+}
+
+// output parameter column i (0 <= i < out_n_params)
+FITOCT_HD inline OutSpec out_spec(const OutModel& m, int i) {
+  if (i < m.D) return {S_RAW, i};
+  i -= m.D;
+  if (m.fam == FITOCT_PRIOR_LASSO) {
+    // ⚑ lassoPrior.stan has no lambda parameter: its penalty lambda_s is data
+    // (lassoPrior.stan:4), exposed as the constant column `lambda`
+    if (i == 0) return {S_LAMBDA_DATA, 0};
+    i -= 1;
+  } else if (m.fam == FITOCT_PRIOR_HORSESHOE) {
+    // transformed parameters of horseShoePrior.stan:25-33, in declaration order
+    if (i == 0) return {S_TAU, 0};
+    i -= 1;
+    if (i < m.Nn) return {S_HS_LAMBDA, i};
+    i -= m.Nn;
+    if (i < m.Nn) return {S_HS_YGP, i};
+    i -= m.Nn;
+  }
+  return {S_RAW, m.D};   // br (plotExpGP.R:42-43: absent in a prior run)
+}
+
+// constrained raw parameters r[0..D-1], br r[D]  ->  the value of one output column
+// (products and correctly rounded square roots only: the same bits on host and device)
+FITOCT_HD inline double out_value(const OutModel& m, OutSpec c, const double* r) {
+  const int Nn = m.Nn;
+  // horseshoe raw order: theta[3] z[Nn] r1_global r2_global r1_local[Nn] r2_local[Nn] sigma
+  switch (c.src) {
+    case S_RAW: return r[c.k];
+    case S_LAMBDA_DATA: return m.lambda_scale;
+    case S_TAU: return r[3 + Nn] * sqrt(r[4 + Nn]);
+    case S_HS_LAMBDA: return r[5 + Nn + c.k] * sqrt(r[5 + 2 * Nn + c.k]);
+    default: {   // S_HS_YGP
+      const double tau = r[3 + Nn] * sqrt(r[4 + Nn]);
+      return r[3 + c.k] * (r[5 + Nn + c.k] * sqrt(r[5 + 2 * Nn + c.k])) * tau;
+    }
+  }
+}
+
+// ---- quantiles ----------------------------------------------------------------------------
+// Order-preserving 64-bit key of a double: key(a) < key(b) as unsigned integers where a < b,
+// with -0.0 below +0.0 (a total order, so that an order statistic is one bit pattern).
+FITOCT_HD inline uint64_t order_key(double v) {
+  uint64_t u;
+  memcpy(&u, &v, sizeof u);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+FITOCT_HD inline double key_value(uint64_t k) {
+  const uint64_t u = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k;
+  double v;
+  memcpy(&v, &u, sizeof v);
+  return v;
+}
+// type-7 quantile of S sorted values at probability p: x[lo] + frac (x[hi] - x[lo])
+struct QIndex {
+  int64_t lo, hi;
+  double frac;
+};
+FITOCT_HD inline QIndex quantile_index(int64_t S, double p) {
+  const double h = (double)(S - 1) * p, fl = floor(h);
+  QIndex q;
+  q.lo = (int64_t)fl < S - 1 ? (int64_t)fl : S - 1;
+  q.hi = q.lo + 1 < S ? q.lo + 1 : S - 1;
+  q.frac = h - fl;
+  return q;
+}
+// (called on the host only, by both routes: a device compile could contract it to an fma)
+inline double quantile_lerp(double x_lo, double x_hi, double frac) {
+  return frac > 0.0 ? x_lo + frac * (x_hi - x_lo) : x_lo;
+}
+
+// ---- diagnostics (stan::analyze, as printed by rstan::summary) ------------------------------
+inline double mean_of(const double* x, int n) {
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += x[i];
+  return s / n;
+}
+inline double var_of(const double* x, int n) {  // sample variance (n-1)
+  const double m = mean_of(x, n);
+  double s = 0.0;
+  for (int i = 0; i < n; ++i) s += (x[i] - m) * (x[i] - m);
+  return s / (n - 1);
+}
+
+// potential scale reduction from the means cm[m] and sample variances cv[m] of m already
+// split chains of n draws
+inline double psr_moments(const double* cm, const double* cv, int m, int n) {
+  const double B = n * var_of(cm, m);
+  const double W = mean_of(cv, m);
+  return sqrt((B / W + n - 1) / n);
+}
+
+// stan::analyze::compute_effective_sample_size on m already split chains of n draws, from
+// their means cm[m], sample variances cvar[m] and acov_mean(lag): the mean over chains of
+// the biased autocovariance at `lag` (each chain about its own mean).  Geyer's initial
+// positive sequence, then the initial monotone sequence, then the 1/log10 floor.
+template <class F>
+double ess_moments(const double* cm, const double* cvar, int m, int n, F&& acov_mean) {
+  const double mean_var = mean_of(cvar, m);
+  double var_plus = mean_var * (n - 1) / n;
+  if (m > 1) var_plus += var_of(cm, m);
+  if (!(var_plus > 0.0)) return NAN;
+  std::vector<double> rho(n + 2, 0.0);
+  double rho_even = 1.0;
+  double rho_odd = 1.0 - (mean_var - acov_mean(1)) / var_plus;
+  rho[0] = 1.0;
+  rho[1] = rho_odd;
+  int t = 1;
+  while (t < n - 4 && (rho_even + rho_odd) > 0.0) {
+    rho_even = 1.0 - (mean_var - acov_mean(t + 1)) / var_plus;
+    rho_odd = 1.0 - (mean_var - acov_mean(t + 2)) / var_plus;
+    if ((rho_even + rho_odd) >= 0.0) {
+      rho[t + 1] = rho_even;
+      rho[t + 2] = rho_odd;
+    }
+    t += 2;
+  }
+  const int max_t = t;
+  if (rho_even > 0.0) rho[max_t + 1] = rho_even;
+  t = 1;
+  while (t <= max_t - 2) {
+    if (rho[t + 1] + rho[t + 2] > rho[t - 1] + rho[t]) {
+      rho[t + 1] = (rho[t - 1] + rho[t]) / 2.0;
+      rho[t + 2] = rho[t + 1];
+    }
+    t += 2;
+  }
+  const double ess = (double)m * n;
+  double tau = -1.0;
+  for (int i = 0; i <= max_t; ++i) tau += 2.0 * rho[i];
+  tau += rho[max_t + 1];
+  tau = std::max(tau, 1.0 / log10(ess));
+  return ess / tau;
+}
+
+}  // namespace fitoct

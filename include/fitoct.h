@@ -15,6 +15,8 @@
  *   fitoct_build_basis()    <- the GP design of server.R:623-650 (xGP grid, SE kernel)
  *   fitoct_split_rhat_ess() <- rstan::summary(...)$summary[, c('n_eff','Rhat')]
  *                              (server.R:88-104,189-213)
+ *   fitoct_summary_*()      <- the whole rstan::summary(fit, pars)$summary table (mean, sd,
+ *                              quantiles, n_eff, Rhat) of draws that stay in HBM
  *   fitoct_plan_*()         <- same as fitoct_expgp_sample, split so that inputs can stay
  *                              resident in HBM across calls and draws can land in a
  *                              caller-owned device buffer (multi-GPU gather / benchmarking)
@@ -490,6 +492,51 @@ int32_t fitoct_split_rhat_ess(const double* x, int32_t chains, int32_t n,
                               double* rhat, double* ess);
 /* rank-normalised split-R-hat (Vehtari et al. 2021), max of bulk and folded. */
 int32_t fitoct_rank_rhat(const double* x, int32_t chains, int32_t n, double* rhat);
+
+/* ---- posterior summary (added within ABI 8: new entries only, no struct above changed) ---- *
+ * rstan::summary(fit, pars)$summary (plotExpGP.R:10 print(fit, pars); server.R:88-104,189-213)
+ * of draws that stay in HBM: per output column, over the post-warmup draws pooled over
+ * chains, mean, se_mean = sd / sqrt(n_eff), sd (n - 1), the type-7 quantiles
+ * (h = (S-1) p: x[floor h] + (h - floor h) (x[floor h + 1] - x[floor h])), and n_eff / Rhat
+ * exactly as fitoct_split_rhat_ess gives them (NaN when every chain is constant).  A column
+ * that holds a NaN gives an all-NaN row, for that group only.  Results are the same bit for
+ * bit from call to call. */
+typedef struct fitoct_summary_config {
+  int32_t first_iter;          /* leading saved iterations to skip (the saved warmup) */
+  int32_t n_probs;             /* 0..16 */
+  double  probs[16];           /* each in [0, 1]; default 0.025 0.25 0.5 0.75 0.975 (rstan) */
+  int64_t max_staging_bytes;   /* 0 = library default (256 MiB); cap on the column-major staging
+                                  buffer: more columns than fit are processed in several passes
+                                  (never less than one column per pass) */
+  int32_t device;              /* ordinal of the device d_draws lives on */
+} fitoct_summary_config;
+void fitoct_default_summary_config(fitoct_summary_config* cfg);
+int32_t fitoct_summary_width(int32_t n_probs);                 /* 5 + n_probs */
+/* draws in the sampler's raw layout [n_groups][chains][iters_saved][n_cols] (n_groups = 1 for
+ * a plan; the batch layout otherwise; probs[g] describes group g, all sharing prior_type, Nn,
+ * prior_PD).  out[n_groups][P][5 + n_probs], P = 7 + fitoct_output_n_params(prob): the OUTPUT
+ * layout of fitoct_output_rows (horseshoe tau / lambda.k / yGP.k, lasso's constant lambda, no
+ * br under prior_PD), each row = mean, se_mean, sd, the quantiles, n_eff, Rhat.
+ * Every argument is checked before the first HIP call (FITOCT_E_ARG: fewer than 4 post-warmup
+ * iterations, n_probs outside 0..16, a probability outside [0, 1], NULL pointers, groups that
+ * differ in family, Nn or prior_PD, d_draws not device memory); FITOCT_E_NODEVICE without a
+ * device.  fitoct_summary_device runs on `stream` (hipStream_t; NULL = default stream) and
+ * synchronises it before returning. */
+int32_t fitoct_summary_device(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                              int32_t iters_saved, const void* d_draws,
+                              const fitoct_summary_config* cfg, void* stream, double* out);
+/* the same computation on the host (draws: a host buffer; cfg->device and max_staging_bytes
+ * are ignored): the reference the device route is tested against */
+int32_t fitoct_summary_host(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                            int32_t iters_saved, const double* draws,
+                            const fitoct_summary_config* cfg, double* out);
+/* Summary of the last completed run's draws where they lie: the plan's (batch's) internal
+ * buffer or the caller's d_draws, which is also where a device-list run gathers.  out[P][w]
+ * for a plan, out[n_problems][P][w] for a batch (cfg->device is ignored).  FITOCT_E_ARG
+ * before a run, while a launch is in flight, and for a device-list run whose shards stayed in
+ * per-device internal buffers (pass a d_draws to the run: the summary needs one buffer). */
+int32_t fitoct_plan_summary(fitoct_plan* plan, const fitoct_summary_config* cfg, double* out);
+int32_t fitoct_batch_summary(fitoct_batch* batch, const fitoct_summary_config* cfg, double* out);
 
 #ifdef __cplusplus
 }
