@@ -83,6 +83,10 @@ REPLAY = {
     "minimum": Case(lambda: prob("normal", 2, 2), 8, 10),
     "user_basis_streamed": Case(lambda: user_basis_prob(1000), 8, 10),
     "user_basis_resident": Case(lambda: user_basis_prob(300), 8, 10),
+    # a length scale rho other than 1/Nn, both well conditioned (kappa2 4e3 and 1.3: the
+    # oracle's own basis is the library's to ~1e-13, so the replay means what it says)
+    "rho_wide": Case(lambda: prob("normal", 700, 10, grid="internal", rho=0.15), 8, 8),
+    "rho_overflow_rows": Case(lambda: prob("normal", 1000, 15, rho=0.03), 8, 8),
 }
 
 # row and adaptation checks only

@@ -166,6 +166,20 @@ def test_caller_supplied_basis(name, bpt):
     _check(name, prob, cfg, out)
 
 
+@pytest.mark.parametrize("name,mode,bpt", [("rho_wide", POLY, 4), ("rho_overflow_rows", ROWS, 0)])
+def test_length_scale_other_than_the_default(name, mode, bpt):
+    """rho away from 1/Nn (tests/rho_cases.py): rho 0.15 at Nn = 10, the factorised basis with
+    the geometric moments; rho 0.03 at Nn = 15, where t^14 would overflow and the sampler
+    runs the built-in basis through the streamed-rows fallback."""
+    case = RC.REPLAY[name]
+    prob = case.make()
+    info, cfg, out = _launch(case, prob)
+    assert prob.B is None and prob.rho != 1 / prob.Nn
+    assert info["basis_mode"] == mode and info["bins_per_thread"] == bpt
+    assert info["chains_per_tile"] == 1 and info["sampler"] == SPECULATIVE
+    _check(name, prob, cfg, out)
+
+
 @pytest.mark.parametrize("name", ["mixed_1024", "mixed_300"])
 def test_mixed_precision_rows_and_adaptation(name):
     """precision = "mixed" (f32 sweep): the f64 oracle is not the same chain, so no replay;
