@@ -197,6 +197,13 @@ SIGNATURES = [
      [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(SummaryConfig), _dp]),
     ("fitoct_plan_summary", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
     ("fitoct_batch_summary", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_monitor_device", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SummaryConfig),
+      C.c_void_p, _dp]),
+    ("fitoct_monitor_host", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_plan_monitor", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_batch_monitor", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
 ]
 
 _LIB = None

@@ -272,6 +272,63 @@ def summary_host(draws: np.ndarray, prob, first_iter: int = 0, probs=DEFAULT_PRO
     return out
 
 
+MONITOR_KEYS = ("Rhat", "Rhat_bulk", "Rhat_fold", "Bulk_ESS", "Tail_ESS")
+
+
+def monitor_rows(table: np.ndarray, prob: ExpGPProblem, pars=None) -> dict:
+    """One group's rank-diagnostics table ``[P, 5]`` (``fitoct_monitor_*``) as ``{name: {"Rhat",
+    "Rhat_bulk", "Rhat_fold", "Bulk_ESS", "Tail_ESS"}}`` (``Rhat`` the rank-normalised R-hat:
+    the larger of bulk and folded), all-NaN rows omitted, ``pars`` as in :func:`summary_rows`."""
+    from .stanfit import _base, output_columns
+    names = output_columns(prob)
+    if pars is None:
+        sel = list(range(len(names)))
+    else:
+        sel = []
+        for p in ([pars] if isinstance(pars, str) else pars):
+            hit = [i for i, c in enumerate(names) if c == p or _base(c) == p]
+            if not hit:
+                raise KeyError(f"no parameter {p!r} in the fit")
+            sel += hit
+    return {names[i]: {k: float(v) for k, v in zip(MONITOR_KEYS, table[i])}
+            for i in sel if not np.all(np.isnan(table[i]))}
+
+
+def monitor_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter: int = 0,
+                   max_staging_bytes: int = 0, device: int = 0, stream: int = 0) -> np.ndarray:
+    """``rstan::monitor``'s rank diagnostics of draws that lie in device memory
+    (``fitoct_monitor_device``; arguments as :func:`summary_device`): rank-normalised split
+    R-hat (max, bulk, folded), bulk ESS and tail ESS per output column.  Returns
+    ``[groups, P, 5]`` (rows: :func:`monitor_rows`)."""
+    ps, arr = _problem_array(prob)
+    c = _summary_config(first_iter, (), max_staging_bytes, device)
+    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
+    out = np.empty((len(ps), max(n_out, 0), 5))
+    check(lib().fitoct_monitor_device(arr, len(ps), int(chains), int(iters_saved),
+                                      C.c_void_p(d_draws or None), C.byref(c),
+                                      C.c_void_p(stream or None), dptr(out)))
+    return out
+
+
+def monitor_host(draws: np.ndarray, prob, first_iter: int = 0) -> np.ndarray:
+    """The same table computed on the host (``fitoct_monitor_host``) from raw draws
+    ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
+    ps, arr = _problem_array(prob)
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    if draws.ndim == 3:
+        draws = draws[None]
+    if draws.ndim != 4 or draws.shape[0] != len(ps):
+        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
+    if draws.shape[3] != ps[0].D + 8:
+        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    c = _summary_config(first_iter, ())
+    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
+    out = np.empty((len(ps), max(n_out, 0), 5))
+    check(lib().fitoct_monitor_host(arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws),
+                                    C.byref(c), dptr(out)))
+    return out
+
+
 @dataclass
 class SampleOutput:
     draws: np.ndarray          # [chains, iters_saved, n_cols]
@@ -407,6 +464,17 @@ class Plan:
         check(lib().fitoct_plan_summary(self._h, C.byref(c), dptr(out)))
         return summary_rows(out, self.prob, probs, pars)
 
+    def monitor(self, pars=None, first_iter=None, max_staging_bytes: int = 0) -> dict:
+        """``rstan::monitor``'s rank diagnostics of the last run, computed on the device from
+        the draws where they lie (as :meth:`summary`): the dict of :func:`monitor_rows`."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        c = _summary_config(first_iter, (), max_staging_bytes)
+        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._p))
+        out = np.empty((n_out, 5))
+        check(lib().fitoct_plan_monitor(self._h, C.byref(c), dptr(out)))
+        return monitor_rows(out, self.prob, pars)
+
     def close(self):
         if getattr(self, "_h", None):
             lib().fitoct_plan_destroy(self._h)
@@ -489,6 +557,19 @@ class Batch:
         if problem is not None:
             return summary_rows(out[problem], self.probs[problem], probs, pars)
         return [summary_rows(out[p], self.probs[p], probs, pars) for p in range(len(self.probs))]
+
+    def monitor(self, problem=None, pars=None, first_iter=None, max_staging_bytes: int = 0):
+        """Device rank diagnostics of the last run (:meth:`Plan.monitor`) of every file in one
+        call: a list with one dict per problem, or problem ``problem``'s dict."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        c = _summary_config(first_iter, (), max_staging_bytes)
+        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._arr[0]))
+        out = np.empty((len(self.probs), n_out, 5))
+        check(lib().fitoct_batch_monitor(self._h, C.byref(c), dptr(out)))
+        if problem is not None:
+            return monitor_rows(out[problem], self.probs[problem], pars)
+        return [monitor_rows(out[p], self.probs[p], pars) for p in range(len(self.probs))]
 
     def close(self):
         if getattr(self, "_h", None):

@@ -46,6 +46,8 @@ SOURCES = [
     ("nuts_monoexp", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=3"]),
     # the posterior summary's kernels and entry points (no family parameter)
     ("summary_device", "summary_device.hip", "hipcc", _KERNEL),
+    # the rank diagnostics' kernels (the device sort) and entry points
+    ("monitor_device", "monitor_device.hip", "hipcc", _KERNEL),
     ("fitoct_api", "fitoct_api.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("multi_device", "multi_device.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("host_model", "host_model.cpp", "g++", ["-O2", "-std=c++17"]),
@@ -55,7 +57,7 @@ SOURCES = [
     ("stamps_report", "stamps_report.cpp", "g++", ["-O2", "-std=c++17"]),
 ]
 # objects whose kernels' resource remarks are kept beside them (<object>.resources.txt)
-RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["summary_device"]
+RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["summary_device", "monitor_device"]
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")

@@ -185,38 +185,7 @@ int split_rhat_ess(const double* x, int chains, int n, double* rhat, double* ess
 }
 
 // rank-normalised split-R-hat (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021)
-static double inv_normal_cdf(double p) {
-  // Acklam's rational approximation + one Newton step (|err| < 1e-13)
-  static const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02,
-                             -2.759285104469687e+02, 1.383577518672690e+02,
-                             -3.066479806614716e+01, 2.506628277459239e+00};
-  static const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02,
-                             -1.556989798598866e+02, 6.680131188771972e+01,
-                             -1.328068155288572e+01};
-  static const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01,
-                             -2.400758277161838e+00, -2.549732539343734e+00,
-                             4.374664141464968e+00, 2.938163982698783e+00};
-  static const double d[] = {7.784695709041462e-03, 3.224671290700398e-01,
-                             2.445134137142996e+00, 3.754408661907416e+00};
-  double q, r, x;
-  if (p < 0.02425) {
-    q = sqrt(-2 * log(p));
-    x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-        ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
-  } else if (p > 1 - 0.02425) {
-    q = sqrt(-2 * log(1 - p));
-    x = -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
-        ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
-  } else {
-    q = p - 0.5;
-    r = q * q;
-    x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
-        (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1);
-  }
-  const double e = 0.5 * erfc(-x / sqrt(2.0)) - p;
-  const double u = e * sqrt(2 * M_PI) * exp(x * x / 2);
-  return x - u / (1 + x * u / 2);
-}
+// (inv_normal_cdf lives in summary_shared.h: the device rank diagnostics compile the same copy)
 
 static void rank_normalise(const std::vector<double>& v, std::vector<double>& z) {
   const size_t S = v.size();
@@ -234,12 +203,14 @@ static void rank_normalise(const std::vector<double>& v, std::vector<double>& z)
   }
 }
 
-int rank_rhat(const double* x, int chains, int n, double* out) {
-  if (chains < 1 || n < 4) return fail(FITOCT_E_ARG, "need >= 1 chain and >= 4 draws");
+// the split draws pooled in split-chain order, their rank-normalised scores z1 and those of the
+// draws folded about the pooled median, z2 (x[chains][n], h = n / 2)
+static void rank_series(const double* x, int chains, int n, std::vector<double>& pooled,
+                        std::vector<double>& z1, std::vector<double>& z2) {
   const int h = n / 2;
   // split, then rank-normalise pooled split draws
-  std::vector<double> pooled, folded;
-  std::vector<int> off;
+  std::vector<double> folded;
+  pooled.clear();
   for (int c = 0; c < chains; ++c)
     for (int half = 0; half < 2; ++half) {
       const double* base = x + (size_t)c * n + (half ? n - h : 0);
@@ -253,15 +224,65 @@ int rank_rhat(const double* x, int chains, int n, double* out) {
     med = 0.5 * (med + lo);
   }
   for (double v : pooled) folded.push_back(fabs(v - med));
-  std::vector<double> z1, z2;
   rank_normalise(pooled, z1);
   rank_normalise(folded, z2);
-  std::vector<const double*> c1, c2;
-  for (int j = 0; j < 2 * chains; ++j) {
-    c1.push_back(z1.data() + (size_t)j * h);
-    c2.push_back(z2.data() + (size_t)j * h);
+}
+
+static std::vector<const double*> split_rows(const std::vector<double>& z, int m, int h) {
+  std::vector<const double*> c;
+  for (int j = 0; j < m; ++j) c.push_back(z.data() + (size_t)j * h);
+  return c;
+}
+
+int rank_rhat(const double* x, int chains, int n, double* out) {
+  if (chains < 1 || n < 4) return fail(FITOCT_E_ARG, "need >= 1 chain and >= 4 draws");
+  const int h = n / 2;
+  std::vector<double> pooled, z1, z2;
+  rank_series(x, chains, n, pooled, z1, z2);
+  *out = std::max(psr(split_rows(z1, 2 * chains, h), h), psr(split_rows(z2, 2 * chains, h), h));
+  return FITOCT_OK;
+}
+
+// rstan::monitor's rank diagnostics of one scalar (include/fitoct.h "rank diagnostics"):
+// out[5] = Rhat_rank, Rhat_bulk, Rhat_fold, Bulk_ESS, Tail_ESS
+int monitor_column(const double* x, int chains, int n, double* out) {
+  if (chains < 1 || n < 4) return fail(FITOCT_E_ARG, "need >= 1 chain and >= 4 draws");
+  const int h = n / 2, m = 2 * chains;
+  // a NaN, or every chain constant (W = 0: the R-hats would be rounding noise over zero), among
+  // the split draws: an odd n's middle draw takes no part
+  bool has_nan = false, constant = true;
+  for (int c = 0; c < chains; ++c)
+    for (int i = 0; i < n; ++i)
+      if (i < h || i >= n - h) {
+        const double v = x[(size_t)c * n + i];
+        has_nan = has_nan || v != v;
+        constant = constant && v == x[(size_t)c * n];
+      }
+  if (has_nan || constant) {
+    for (int i = 0; i < 5; ++i) out[i] = NAN;
+    return FITOCT_OK;
   }
-  *out = std::max(psr(c1, h), psr(c2, h));
+  std::vector<double> pooled, z1, z2;
+  rank_series(x, chains, n, pooled, z1, z2);
+  const int64_t S = (int64_t)pooled.size();
+  // the order statistics by the total order of the keys, as the device route sorts them
+  std::vector<uint64_t> keys((size_t)S);
+  for (int64_t i = 0; i < S; ++i) keys[i] = order_key(pooled[i]);
+  std::sort(keys.begin(), keys.end());
+  out[1] = psr(split_rows(z1, m, h), h);
+  out[2] = psr(split_rows(z2, m, h), h);
+  out[0] = std::max(out[1], out[2]);
+  out[3] = ess_chains(split_rows(z1, m, h), h);
+  double tail[2];
+  const double tp[2] = {0.05, 0.95};
+  std::vector<double> ind((size_t)S);
+  for (int t = 0; t < 2; ++t) {
+    const QIndex qi = quantile_index(S, tp[t]);
+    const double q = quantile_lerp(key_value(keys[qi.lo]), key_value(keys[qi.hi]), qi.frac);
+    for (int64_t i = 0; i < S; ++i) ind[i] = pooled[i] <= q ? 1.0 : 0.0;
+    tail[t] = ess_chains(split_rows(ind, m, h), h);   // NaN for a constant indicator
+  }
+  out[4] = tail_min(tail[0], tail[1]);
   return FITOCT_OK;
 }
 

@@ -4,7 +4,8 @@
 // buffer, and the same computation on the host (fitoct_summary_host, on top of
 // split_rhat_ess and std::nth_element) that the device route is tested against.
 //
-// Device route, per pass over a chunk of output columns:
+// Device route, per pass over a chunk of output columns (the first three kernels and Geyer's
+// rounds live in summary_kernels.h, shared with monitor_device.hip):
 //   stage_kernel    raw rows (contiguous, read coalesced through LDS) -> the output-layout
 //                   transform (summary_shared.h, the copy stan_output.cpp uses) -> a
 //                   column-major post-warmup staging buffer X[group][col][chain][n];
@@ -32,77 +33,15 @@
 #include "fitoct.h"
 #include "host_internal.h"
 #include "plan_internal.h"
+#include "summary_kernels.h"
 #include "summary_shared.h"
 
 namespace fitoct {
 namespace {
 
-constexpr int64_t DEFAULT_STAGING_BYTES = (int64_t)256 << 20;
-constexpr int MAX_PROBS = 16;
 constexpr int QT_MAX = 2 * MAX_PROBS;   // order statistics per column: x[lo], x[hi] per probability
-constexpr int LAG_BLOCK = 64;           // lags per acov_kernel workgroup: one per lane
-constexpr int STAGE_ROWS = 32;          // rows of one chain per stage_kernel workgroup
-constexpr int STAGE_THREADS = 256;
-constexpr int ACOV_WAVES = 4;
-constexpr int ACOV_TILE = 512;          // series elements per LDS tile and wave
 constexpr int QHIST_THREADS = 256;
 constexpr int QHIST_PER_THREAD = 16;    // elements per thread and grid stride
-
-// What a call computes: shapes checked by check_args.
-struct Shape {
-  int G = 0, C = 0, I = 0, W = 0;   // groups, chains, saved iterations, raw columns
-  int first = 0, n = 0, h = 0, m = 0;   // skipped, post-warmup, half length, split chains
-  int P = 0, np = 0, width = 0;     // output columns, probabilities, 5 + np
-  int64_t S = 0;                    // pooled draws of one column
-  OutModel model{};                 // lambda_scale: per group, in lscale
-  std::vector<double> lscale;
-};
-
-int check_args(const fitoct_problem* probs, int n_groups, int chains, int iters_saved,
-               const void* draws, const fitoct_summary_config* cfg, const double* out,
-               Shape& s) {
-  if (!probs || !cfg || !out || !draws)
-    return fail(FITOCT_E_ARG, "summary: NULL argument (problems, draws, config or out)");
-  if (n_groups < 1 || chains < 1 || iters_saved < 1)
-    return fail(FITOCT_E_ARG, "summary: need n_groups, chains and iters_saved >= 1");
-  if (chains > (1 << 30)) return fail(FITOCT_E_ARG, "summary: too many chains");
-  const fitoct_problem& p0 = probs[0];
-  const int D = model_dim(p0.prior_type, p0.Nn);
-  if (D < 0) return fail(FITOCT_E_ARG, "summary: unknown prior_type");
-  if (p0.prior_type != FITOCT_MODEL_MONOEXP && (p0.Nn < 2 || p0.Nn > 24))
-    return fail(FITOCT_E_ARG, "summary: Nn must be in [2, 24]");
-  for (int g = 1; g < n_groups; ++g)
-    if (probs[g].prior_type != p0.prior_type || probs[g].Nn != p0.Nn ||
-        (probs[g].prior_PD != 0) != (p0.prior_PD != 0))
-      return fail(FITOCT_E_ARG, "summary: groups must share prior_type, Nn and prior_PD (group " +
-                                    std::to_string(g) + ")");
-  if (cfg->first_iter < 0) return fail(FITOCT_E_ARG, "summary: first_iter is negative");
-  if ((int64_t)iters_saved - cfg->first_iter < 4)
-    return fail(FITOCT_E_ARG, "summary: need >= 4 post-warmup iterations (iters_saved - first_iter)");
-  if (cfg->n_probs < 0 || cfg->n_probs > MAX_PROBS)
-    return fail(FITOCT_E_ARG, "summary: n_probs must be in [0, 16]");
-  for (int i = 0; i < cfg->n_probs; ++i)
-    if (!(cfg->probs[i] >= 0.0 && cfg->probs[i] <= 1.0))
-      return fail(FITOCT_E_ARG, "summary: probs[" + std::to_string(i) + "] is not in [0, 1]");
-  if (cfg->max_staging_bytes < 0)
-    return fail(FITOCT_E_ARG, "summary: max_staging_bytes is negative");
-  s.G = n_groups;
-  s.C = chains;
-  s.I = iters_saved;
-  s.W = D + 8;
-  s.first = cfg->first_iter;
-  s.n = iters_saved - cfg->first_iter;
-  s.h = s.n / 2;   // the middle draw is dropped when n is odd
-  s.m = 2 * chains;
-  s.model = {p0.prior_type, p0.Nn, D, p0.prior_PD ? 1 : 0, p0.lambda_scale};
-  s.P = 7 + out_n_params(s.model);
-  s.np = cfg->n_probs;
-  s.width = 5 + s.np;
-  s.S = (int64_t)chains * s.n;
-  s.lscale.resize(n_groups);
-  for (int g = 0; g < n_groups; ++g) s.lscale[g] = probs[g].lambda_scale;
-  return FITOCT_OK;
-}
 
 // out row = mean, se_mean, sd, the quantiles, n_eff, Rhat
 void put_row(const Shape& s, double* row, double mean, double sd, const double* q, double ess,
@@ -116,11 +55,6 @@ void put_row(const Shape& s, double* row, double mean, double sd, const double* 
 }
 void nan_row(const Shape& s, double* row) {
   for (int i = 0; i < s.width; ++i) row[i] = NAN;
-}
-
-// output column j of a raw row (7 sampler columns, then the parameter columns)
-FITOCT_HD inline double column_value(const OutModel& m, int j, const double* raw) {
-  return j < 7 ? raw[j] : out_value(m, out_spec(m, j - 7), raw + 7);
 }
 
 // ---- host route -----------------------------------------------------------------------------
@@ -173,134 +107,7 @@ int summary_host(const Shape& s, const double* draws, const fitoct_summary_confi
   return FITOCT_OK;
 }
 
-// ---- kernels --------------------------------------------------------------------------------
-// What every kernel needs of the call (by value: a few words).
-struct KShape {
-  int G, C, I, W, first, n, h, m;
-  int c0, ncc;          // this pass: first output column and number of columns
-  OutModel model;
-};
-
-// X[pair = g * ncc + jc][chain][n]
-__device__ inline const double* chain_series(const double* X, const KShape& k, int64_t pair,
-                                             int chain) {
-  return X + ((size_t)pair * k.C + chain) * k.n;
-}
-
-// one workgroup per (group, chain, block of STAGE_ROWS rows)
-__global__ __launch_bounds__(STAGE_THREADS) void stage_kernel(KShape k, const double* draws,
-                                                              const double* lscale, double* X) {
-  extern __shared__ double tile[];   // [STAGE_ROWS][Wp], Wp odd: rows land on different banks
-  const int Wp = k.W | 1;
-  const int rblocks = (k.n + STAGE_ROWS - 1) / STAGE_ROWS;
-  int64_t b = blockIdx.x;
-  const int rb = (int)(b % rblocks);
-  b /= rblocks;
-  const int c = (int)(b % k.C), g = (int)(b / k.C);
-  const int i0 = rb * STAGE_ROWS, rows = min(STAGE_ROWS, k.n - i0);
-  const double* src = draws + (((size_t)g * k.C + c) * k.I + k.first + i0) * k.W;
-  for (int t = threadIdx.x; t < rows * k.W; t += STAGE_THREADS) {
-    const int r = t / k.W;
-    tile[r * Wp + (t - r * k.W)] = src[t];
-  }
-  __syncthreads();
-  OutModel m = k.model;
-  m.lambda_scale = lscale[g];
-  for (int t = threadIdx.x; t < k.ncc * STAGE_ROWS; t += STAGE_THREADS) {
-    const int jc = t / STAGE_ROWS, r = t % STAGE_ROWS;
-    if (r < rows)
-      X[(((size_t)g * k.ncc + jc) * k.C + c) * k.n + i0 + r] =
-          column_value(m, k.c0 + jc, tile + r * Wp);
-  }
-}
-
-__device__ inline double wave_sum(double v) {   // butterfly: every lane gets the same bits
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-  return v;
-}
-
-// mom[pair][split chain][4] = mean, centred sum of squares, sum, the middle draw (first half of
-// an odd-length chain; 0 otherwise); flags: bit 0 a NaN, bit 1 a value that differs from the
-// chain's first draw.  One wave per (pair, split chain).
-__global__ __launch_bounds__(64) void moments_kernel(KShape k, const double* X, double* mom,
-                                                     int* flags) {
-  const int64_t b = blockIdx.x;
-  const int64_t pair = b / k.m;
-  const int j = (int)(b % k.m), lane = threadIdx.x;
-  const double* base = chain_series(X, k, pair, j >> 1);
-  const double* x = base + ((j & 1) ? k.n - k.h : 0);
-  const double first = base[0];
-  double sum = 0.0;
-  int f = 0;
-  for (int i = lane; i < k.h; i += 64) {
-    const double v = x[i];
-    sum += v;
-    f |= (v != v ? 1 : 0) | (v != first ? 2 : 0);
-  }
-  double mid = 0.0;
-  if (!(j & 1) && (k.n & 1)) {
-    mid = base[k.h];
-    f |= (mid != mid ? 1 : 0) | (mid != first ? 2 : 0);
-  }
-  sum = wave_sum(sum);
-  const double mean = sum / k.h;
-  double ssq = 0.0;
-  for (int i = lane; i < k.h; i += 64) {
-    const double d = x[i] - mean;
-    ssq += d * d;
-  }
-  ssq = wave_sum(ssq);
-  const int any = (__ballot(f & 1) ? 1 : 0) | (__ballot(f & 2) ? 2 : 0);
-  if (lane == 0) {
-    double* o = mom + (size_t)b * 4;
-    o[0] = mean;
-    o[1] = ssq;
-    o[2] = sum;
-    o[3] = mid;
-    flags[b] = any;
-  }
-}
-
-// acov[a][l] for the a-th active pair: mean over split chains of the biased autocovariance
-// at lag lag0 + l.  Wave w takes split chains w, w + 4, ...; lane l takes lag lag0 + l; each
-// chain's sum runs over the series in order, the waves' partial means are added in wave order.
-__global__ __launch_bounds__(ACOV_WAVES * 64) void acov_kernel(KShape k, const double* X,
-                                                               const double* mom, const int* act,
-                                                               int lag0, double* acov) {
-  __shared__ double A[ACOV_WAVES][ACOV_TILE];                // centred x[i]
-  __shared__ double B[ACOV_WAVES][ACOV_TILE + LAG_BLOCK];    // centred x[i + lag0 + l]
-  __shared__ double part[ACOV_WAVES][LAG_BLOCK];
-  const int64_t pair = act[blockIdx.x];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  double tot = 0.0;
-  for (int jb = 0; jb < k.m; jb += ACOV_WAVES) {   // (uniform trip count: barriers inside)
-    const int j = jb + w;
-    const bool on = j < k.m;
-    const double* x = on ? chain_series(X, k, pair, j >> 1) + ((j & 1) ? k.n - k.h : 0) : nullptr;
-    const double cm = on ? mom[((size_t)pair * k.m + j) * 4] : 0.0;
-    double s = 0.0;
-    for (int i0 = 0; i0 < k.h; i0 += ACOV_TILE) {
-      for (int t = lane; t < ACOV_TILE; t += 64)
-        A[w][t] = (on && i0 + t < k.h) ? x[i0 + t] - cm : 0.0;
-      for (int t = lane; t < ACOV_TILE + LAG_BLOCK; t += 64) {
-        const int64_t idx = (int64_t)i0 + lag0 + t;
-        B[w][t] = (on && idx < k.h) ? x[idx] - cm : 0.0;
-      }
-      __syncthreads();
-      for (int t = 0; t < ACOV_TILE; ++t) s += A[w][t] * B[w][t + lane];
-      __syncthreads();
-    }
-    if (on) tot += s / k.h;
-  }
-  part[w][lane] = tot;
-  __syncthreads();
-  if (w == 0) {
-    double v = part[0][lane];
-    for (int q = 1; q < ACOV_WAVES; ++q) v += part[q][lane];
-    acov[(size_t)blockIdx.x * LAG_BLOCK + lane] = v / k.m;
-  }
-}
-
+// ---- kernels (stage_kernel, moments_kernel, acov_kernel: summary_kernels.h) ------------------
 // Radix-select state of one pair: T targets (order statistics), each with the key prefix found
 // so far, its rank among the keys sharing that prefix, and the histogram slot of its prefix
 // (targets with equal prefixes share one).
@@ -376,45 +183,12 @@ __global__ __launch_bounds__(64) void qselect_kernel(QState q) {
 }
 
 // ---- device route ---------------------------------------------------------------------------
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
-    return FITOCT_OK;
-  }
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-// the calling thread's device is put back when the call returns
-struct DeviceKeep {
-  int dev = -1;
-  DeviceKeep() {
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  }
-  ~DeviceKeep() {
-    if (dev >= 0) (void)hipSetDevice(dev);
-  }
-};
-struct NeedLag {};   // Geyer's rule asked for a lag block that has not been computed yet
-
-#define FITOCT_TRY(expr)          \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_) return rc_;          \
-  } while (0)
-
 int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_config* cfg,
                    hipStream_t st, double* out) {
   DeviceKeep keep;
   HIP_TRY(hipSetDevice(cfg->device));
   const int64_t col_bytes = (int64_t)s.G * s.S * (int64_t)sizeof(double);
-  const int64_t cap = cfg->max_staging_bytes > 0 ? cfg->max_staging_bytes : DEFAULT_STAGING_BYTES;
-  const int ncc_max = (int)std::max<int64_t>(1, std::min<int64_t>(s.P, cap / col_bytes));
+  const int ncc_max = columns_per_pass(s, cfg, col_bytes);
   const int64_t pairs_max = (int64_t)s.G * ncc_max;
   const int rblocks = (s.n + STAGE_ROWS - 1) / STAGE_ROWS;
   const int nblk = (int)std::max<int64_t>(
@@ -426,13 +200,11 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
     return fail(FITOCT_E_ARG, "summary: shape too large for one launch (lower max_staging_bytes)");
   const int T = 2 * s.np;
 
-  DevBuf X, mom, flags, lscale, acov, act, hist, rank, pre, slot, uniq, nuniq;
+  DevBuf X, lscale, hist, rank, pre, slot, uniq, nuniq;
+  EssBufs eb;
   FITOCT_TRY(X.alloc((size_t)pairs_max * s.S * sizeof(double)));
-  FITOCT_TRY(mom.alloc((size_t)pairs_max * s.m * 4 * sizeof(double)));
-  FITOCT_TRY(flags.alloc((size_t)pairs_max * s.m * sizeof(int)));
+  FITOCT_TRY(eb.alloc(pairs_max, s.m));
   FITOCT_TRY(lscale.alloc((size_t)s.G * sizeof(double)));
-  FITOCT_TRY(acov.alloc((size_t)pairs_max * LAG_BLOCK * sizeof(double)));
-  FITOCT_TRY(act.alloc((size_t)pairs_max * sizeof(int)));
   if (T > 0) {
     FITOCT_TRY(hist.alloc((size_t)pairs_max * QT_MAX * 256 * sizeof(unsigned long long)));
     FITOCT_TRY(rank.alloc((size_t)pairs_max * QT_MAX * sizeof(long long)));
@@ -455,8 +227,8 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
     }
   }
 
-  std::vector<double> h_mom, h_acov, cm(s.m), cv(s.m), q((size_t)std::max(1, s.np));
-  std::vector<int> h_flags, h_act;
+  std::vector<double> h_mom, cm(s.m), cv(s.m), q((size_t)std::max(1, s.np));
+  std::vector<int> h_flags;
   std::vector<unsigned long long> h_keys;
   for (int c0 = 0; c0 < s.P; c0 += ncc_max) {
     const int ncc = std::min(ncc_max, s.P - c0);
@@ -466,16 +238,7 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
                    sizeof(double) * STAGE_ROWS * (s.W | 1), st>>>(
         k, (const double*)d_draws, lscale.as<double>(), X.as<double>());
     HIP_TRY(hipGetLastError());
-    moments_kernel<<<dim3((unsigned)(pairs * s.m)), dim3(64), 0, st>>>(k, X.as<double>(),
-                                                                       mom.as<double>(),
-                                                                       flags.as<int>());
-    HIP_TRY(hipGetLastError());
-    h_mom.resize((size_t)pairs * s.m * 4);
-    h_flags.resize((size_t)pairs * s.m);
-    HIP_TRY(hipMemcpyAsync(h_mom.data(), mom.p, sizeof(double) * h_mom.size(),
-                           hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(h_flags.data(), flags.p, sizeof(int) * h_flags.size(),
-                           hipMemcpyDeviceToHost, st));
+    FITOCT_TRY(queue_moments(k, X.as<double>(), pairs, eb, st, h_mom, h_flags));
 
     // quantiles: queued behind the moments, read back after the autocovariance rounds
     if (T > 0) {
@@ -505,9 +268,8 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
 
     // per pair: NaN / constant pattern, pooled mean and sd, Rhat; which pairs need n_eff
     struct Col {
-      double mean = NAN, sd = NAN, rhat = NAN, ess = NAN;
-      bool has_nan = false, constant = false, done = true;
-      std::vector<double> acov;   // lag blocks computed so far
+      double mean = NAN, sd = NAN, rhat = NAN;
+      bool has_nan = false, constant = false;
     };
     std::vector<Col> cols((size_t)pairs);
     std::vector<int> active;
@@ -542,43 +304,11 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
         cv[j] = mo[4 * j + 1] / (s.h - 1);
       }
       c.rhat = psr_moments(cm.data(), cv.data(), s.m, s.h);
-      c.done = false;
       active.push_back((int)p);
     }
     // n_eff: autocovariance in blocks of 64 lags, only for the columns still undecided
-    for (int lag0 = 0; !active.empty(); lag0 += LAG_BLOCK) {
-      HIP_TRY(hipMemcpyAsync(act.p, active.data(), sizeof(int) * active.size(),
-                             hipMemcpyHostToDevice, st));
-      acov_kernel<<<dim3((unsigned)active.size()), dim3(ACOV_WAVES * 64), 0, st>>>(
-          k, X.as<double>(), mom.as<double>(), act.as<int>(), lag0, acov.as<double>());
-      HIP_TRY(hipGetLastError());
-      h_acov.resize(active.size() * LAG_BLOCK);
-      HIP_TRY(hipMemcpyAsync(h_acov.data(), acov.p, sizeof(double) * h_acov.size(),
-                             hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      std::vector<int> still;
-      for (size_t a = 0; a < active.size(); ++a) {
-        Col& c = cols[active[a]];
-        c.acov.insert(c.acov.end(), h_acov.begin() + a * LAG_BLOCK,
-                      h_acov.begin() + (a + 1) * LAG_BLOCK);
-        const double* mo = h_mom.data() + (size_t)active[a] * s.m * 4;
-        for (int j = 0; j < s.m; ++j) {
-          cm[j] = mo[4 * j];
-          cv[j] = mo[4 * j + 1] / (s.h - 1);
-        }
-        try {
-          c.ess = ess_moments(cm.data(), cv.data(), s.m, s.h, [&](int lag) {
-            if (lag >= s.h) return 0.0;
-            if ((size_t)lag >= c.acov.size()) throw NeedLag{};
-            return c.acov[lag];
-          });
-          c.done = true;
-        } catch (const NeedLag&) {
-          still.push_back(active[a]);
-        }
-      }
-      active.swap(still);
-    }
+    std::vector<double> ess((size_t)pairs, NAN);
+    FITOCT_TRY(ess_rounds(k, X.as<double>(), eb, st, h_mom, active, ess));
     for (int64_t p = 0; p < pairs; ++p) {
       const int g = (int)(p / ncc), j = c0 + (int)(p % ncc);
       double* row = out + ((size_t)g * s.P + j) * s.width;
@@ -590,7 +320,7 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
       for (int i = 0; i < s.np; ++i)
         q[i] = quantile_lerp(key_value(h_keys[p * QT_MAX + 2 * i]),
                              key_value(h_keys[p * QT_MAX + 2 * i + 1]), qidx[i].frac);
-      put_row(s, row, c.mean, c.sd, q.data(), c.ess, c.rhat);
+      put_row(s, row, c.mean, c.sd, q.data(), ess[p], c.rhat);
     }
   }
   return FITOCT_OK;
@@ -600,19 +330,8 @@ int summary_device_checked(const fitoct_problem* probs, int n_groups, int chains
                            const void* d_draws, const fitoct_summary_config* cfg, void* stream,
                            double* out) {
   Shape s;
-  FITOCT_TRY(check_args(probs, n_groups, chains, iters_saved, d_draws, cfg, out, s));
-  if (cfg->device < 0) return fail(FITOCT_E_ARG, "summary: device is negative");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
-    (void)hipGetLastError();
-    return fail(FITOCT_E_NODEVICE, "no HIP device visible");
-  }
-  if (cfg->device >= ndev) return fail(FITOCT_E_ARG, "summary: device ordinal out of range");
-  int bdev = -1;
-  if (buffer_device(d_draws, bdev) != FITOCT_OK) {   // also a pointer the runtime does not know
-    (void)hipGetLastError();
-    return fail(FITOCT_E_ARG, "summary: d_draws must be a device buffer (hipMalloc)");
-  }
+  FITOCT_TRY(check_args("summary", true, probs, n_groups, chains, iters_saved, d_draws, cfg, out, s));
+  FITOCT_TRY(check_device("summary", cfg, d_draws));
   return summary_device(s, d_draws, cfg, (hipStream_t)stream, out);
 }
 
@@ -641,7 +360,7 @@ int32_t fitoct_summary_host(const fitoct_problem* probs, int32_t n_groups, int32
                             const fitoct_summary_config* cfg, double* out) {
   return guarded(__func__, [&]() -> int32_t {
     Shape s;
-    const int rc = check_args(probs, n_groups, chains, iters_saved, draws, cfg, out, s);
+    const int rc = check_args("summary", true, probs, n_groups, chains, iters_saved, draws, cfg, out, s);
     return rc ? rc : summary_host(s, draws, cfg, out);
   });
 }

@@ -1,7 +1,8 @@
-// Pieces of the posterior summary that the host and the device must compute the same way
-// (include/fitoct.h "posterior summary"): the output-layout transform of
-// stan_output.cpp, the order-preserving key and the type-7 index arithmetic of the quantiles,
-// and Geyer's truncation rule of the effective sample size.  Compiles for the host (g++) and,
+// Pieces of the posterior summary and of the rank diagnostics that the host and the device must
+// compute the same way (include/fitoct.h "posterior summary", "rank diagnostics"; DESIGN.md
+// §4): the output-layout transform of stan_output.cpp, the order-preserving key and the type-7
+// index arithmetic of the quantiles, Geyer's truncation rule of the effective sample size, and
+// the inverse normal CDF of the rank normalisation.  Compiles for the host (g++) and,
 // where marked FITOCT_HD, for the device (hipcc).
 #pragma once
 #include <math.h>
@@ -175,6 +176,52 @@ double ess_moments(const double* cm, const double* cvar, int m, int n, F&& acov_
   tau += rho[max_t + 1];
   tau = std::max(tau, 1.0 / log10(ess));
   return ess / tau;
+}
+
+// ---- rank diagnostics (rstan::monitor) ----------------------------------------------------------
+// a NaN among sorted keys lies at an end: below key(-inf) or above key(+inf)
+FITOCT_HD inline bool keys_hold_nan(uint64_t first, uint64_t last) {
+  return first < 0x000fffffffffffffull || last > 0xfff0000000000000ull;
+}
+// Tail_ESS of the two indicator series: the smaller one, a NaN in either propagating
+inline double tail_min(double a, double b) {
+  return (a != a || b != b) ? NAN : std::min(a, b);
+}
+
+// ---- rank normalisation (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021) -----------------
+// Phi^-1 of the fractional rank: the host diagnostics (host_model.cpp) and the device rank
+// diagnostics (monitor_device.hip) compile this one copy.
+FITOCT_HD inline double inv_normal_cdf(double p) {
+  // Acklam's rational approximation + one Newton step (|err| < 1e-13)
+  const double a[] = {-3.969683028665376e+01, 2.209460984245205e+02,
+                      -2.759285104469687e+02, 1.383577518672690e+02,
+                      -3.066479806614716e+01, 2.506628277459239e+00};
+  const double b[] = {-5.447609879822406e+01, 1.615858368580409e+02,
+                      -1.556989798598866e+02, 6.680131188771972e+01,
+                      -1.328068155288572e+01};
+  const double c[] = {-7.784894002430293e-03, -3.223964580411365e-01,
+                      -2.400758277161838e+00, -2.549732539343734e+00,
+                      4.374664141464968e+00, 2.938163982698783e+00};
+  const double d[] = {7.784695709041462e-03, 3.224671290700398e-01,
+                      2.445134137142996e+00, 3.754408661907416e+00};
+  double q, r, x;
+  if (p < 0.02425) {
+    q = sqrt(-2 * log(p));
+    x = (((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
+        ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
+  } else if (p > 1 - 0.02425) {
+    q = sqrt(-2 * log(1 - p));
+    x = -(((((c[0] * q + c[1]) * q + c[2]) * q + c[3]) * q + c[4]) * q + c[5]) /
+        ((((d[0] * q + d[1]) * q + d[2]) * q + d[3]) * q + 1);
+  } else {
+    q = p - 0.5;
+    r = q * q;
+    x = (((((a[0] * r + a[1]) * r + a[2]) * r + a[3]) * r + a[4]) * r + a[5]) * q /
+        (((((b[0] * r + b[1]) * r + b[2]) * r + b[3]) * r + b[4]) * r + 1);
+  }
+  const double e = 0.5 * erfc(-x / sqrt(2.0)) - p;
+  const double u = e * sqrt(2 * M_PI) * exp(x * x / 2);
+  return x - u / (1 + x * u / 2);
 }
 
 }  // namespace fitoct

@@ -185,6 +185,17 @@ class StanFit:
             rows[self.columns[i]] = row
         return rows
 
+    def monitor(self, pars=None):
+        """``rstan::monitor``'s rank diagnostics of the post-warmup draws on the host
+        (``fitoct_monitor_host``): ``{name: {"Rhat", "Rhat_bulk", "Rhat_fold", "Bulk_ESS",
+        "Tail_ESS"}}``, ``Rhat`` being :func:`rank_rhat` of the column.  Needs the raw draws
+        of a sampled fit (:meth:`from_output`)."""
+        if self._source is None or self._source[0] != "sample":
+            raise ValueError("monitor() needs a sampled fit built by StanFit.from_output")
+        from .api import monitor_host, monitor_rows
+        prob, raw = self._source[1], self._source[3]
+        return monitor_rows(monitor_host(raw, prob, self.warmup)[0], prob, pars)
+
     def print(self, pars=None, digits=3):
         s = self.summary(pars)
         if not s:

@@ -17,6 +17,8 @@
  *                              (server.R:88-104,189-213)
  *   fitoct_summary_*()      <- the whole rstan::summary(fit, pars)$summary table (mean, sd,
  *                              quantiles, n_eff, Rhat) of draws that stay in HBM
+ *   fitoct_monitor_*()      <- rstan::monitor's rank-normalised Rhat, Bulk_ESS and Tail_ESS of
+ *                              the same draws
  *   fitoct_plan_*()         <- same as fitoct_expgp_sample, split so that inputs can stay
  *                              resident in HBM across calls and draws can land in a
  *                              caller-owned device buffer (multi-GPU gather / benchmarking)
@@ -537,6 +539,41 @@ int32_t fitoct_summary_host(const fitoct_problem* probs, int32_t n_groups, int32
  * per-device internal buffers (pass a d_draws to the run: the summary needs one buffer). */
 int32_t fitoct_plan_summary(fitoct_plan* plan, const fitoct_summary_config* cfg, double* out);
 int32_t fitoct_batch_summary(fitoct_batch* batch, const fitoct_summary_config* cfg, double* out);
+
+/* ---- rank diagnostics (added within ABI 8: new entries only, no struct above changed) ------ *
+ * rstan::monitor's columns (server.R:88-104,189-213 read Rhat / n_eff of the fit): the
+ * rank-normalised split R-hat, bulk ESS and tail ESS of Vehtari et al. 2021, per output column
+ * of draws that stay in HBM.  Of the n = iters_saved - first_iter post-warmup draws every chain
+ * is split into halves of h = n / 2 (an odd n's middle draw takes no part) and the
+ * S = 2 chains h values are pooled.  z(v) = Phi^-1((r - 3/8) / (S + 1/4)), r the average rank
+ * over ties (ties by ==: -0.0 ties with +0.0).  Each row of five:
+ *   Rhat_rank  max(Rhat_bulk, Rhat_fold): what fitoct_rank_rhat returns
+ *   Rhat_bulk  potential scale reduction of the split chains of z(x)
+ *   Rhat_fold  the same of z(|x - median|), the median of the S pooled values
+ *   Bulk_ESS   the n_eff of fitoct_split_rhat_ess's rule on the split chains of z(x)
+ *   Tail_ESS   the smaller n_eff of the indicator series x <= q05 and x <= q95 (type-7
+ *              quantiles of the pooled values); NaN when either indicator is constant
+ * A column that holds a NaN, or whose every chain is constant (all values equal, or a
+ * per-chain constant such as stepsize__: W = 0, as for fitoct_split_rhat_ess), gives an
+ * all-NaN row, for that group only.  Results are the same bit for bit from call to call and for any
+ * max_staging_bytes.
+ * The entries take fitoct_summary_config and read first_iter, max_staging_bytes and device
+ * (n_probs and probs are ignored); arguments, refusals and statuses are those of the
+ * fitoct_summary_* entry of the same name.  out[n_groups][P][5]. */
+/* keys of one pooled column that one workgroup sorts in LDS; a larger column is sorted by
+ * several workgroups (radix passes over tiles of FITOCT_MONITOR_SORT_TILE keys) */
+#define FITOCT_MONITOR_SORT_LDS_KEYS 4096
+#define FITOCT_MONITOR_SORT_TILE 2048
+/* device doubles per staged draw: max_staging_bytes caps this many buffers of a pass's columns */
+#define FITOCT_MONITOR_STAGING_BUFFERS 7
+int32_t fitoct_monitor_device(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                              int32_t iters_saved, const void* d_draws,
+                              const fitoct_summary_config* cfg, void* stream, double* out);
+int32_t fitoct_monitor_host(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                            int32_t iters_saved, const double* draws,
+                            const fitoct_summary_config* cfg, double* out);
+int32_t fitoct_plan_monitor(fitoct_plan* plan, const fitoct_summary_config* cfg, double* out);
+int32_t fitoct_batch_monitor(fitoct_batch* batch, const fitoct_summary_config* cfg, double* out);
 
 #ifdef __cplusplus
 }
