@@ -27,6 +27,7 @@ STATUS = {
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int32)
+_lp = C.POINTER(C.c_int64)
 
 
 class Problem(C.Structure):
@@ -124,6 +125,8 @@ class SummaryConfig(C.Structure):
 
 MAX_PROBS = 16   # include/fitoct.h fitoct_summary_config.probs
 
+CURVE = {"dL": 1, "m": 2, "resid": 4}   # include/fitoct.h FITOCT_CURVE_*
+
 TERMINATION = {0: "success", 10: "absolute parameter change", 20: "absolute objective change",
                21: "relative objective change", 30: "gradient norm", 31: "relative gradient",
                40: "maximum iterations", -1: "line search failed"}
@@ -204,6 +207,26 @@ SIGNATURES = [
      [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, _dp, C.POINTER(SummaryConfig), _dp]),
     ("fitoct_plan_monitor", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
     ("fitoct_batch_monitor", C.c_int32, [C.c_void_p, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_curves_width", C.c_int32, [C.c_int32]),
+    ("fitoct_curves_device", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+      C.POINTER(SummaryConfig), C.c_void_p, _dp]),
+    ("fitoct_curves_host", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32,
+      C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_plan_curves", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_batch_curves", C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(SummaryConfig), _dp]),
+    ("fitoct_curves_pick_device", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(SummaryConfig),
+      C.c_void_p, C.c_int32, _lp, _dp, _dp, _dp, _dp]),
+    ("fitoct_plan_curves_pick", C.c_int32,
+     [C.c_void_p, C.POINTER(SummaryConfig), C.c_int32, _lp, _dp, _dp, _dp, _dp]),
+    ("fitoct_batch_curves_pick", C.c_int32,
+     [C.c_void_p, C.c_int32, C.POINTER(SummaryConfig), C.c_int32, _lp, _dp, _dp, _dp, _dp]),
+    ("fitoct_plan_curves_pick_params", C.c_int32,
+     [C.c_void_p, C.POINTER(SummaryConfig), C.c_int32, _lp, _dp, _dp]),
+    ("fitoct_batch_curves_pick_params", C.c_int32,
+     [C.c_void_p, C.c_int32, C.POINTER(SummaryConfig), C.c_int32, _lp, _dp, _dp]),
 ]
 
 _LIB = None

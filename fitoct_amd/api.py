@@ -272,6 +272,106 @@ def summary_host(draws: np.ndarray, prob, first_iter: int = 0, probs=DEFAULT_PRO
     return out
 
 
+CURVE_NAMES = ("dL", "m", "resid")   # the order of a curves table's quantity blocks
+
+
+def _curve_bits(what):
+    names = [what] if isinstance(what, str) else list(what)
+    bad = [w for w in names if w not in _lib.CURVE]
+    if bad or not names:
+        raise ValueError(f"what must name some of {CURVE_NAMES}, got {what!r}")
+    bits = 0
+    for w in names:
+        bits |= _lib.CURVE[w]
+    return bits
+
+
+def curves_blocks(table: np.ndarray, probs_list, what, probs=DEFAULT_PROBS) -> list:
+    """The packed table of ``fitoct_curves_*`` as one array ``[nq, N_g, 2 + len(probs)]`` per
+    group (quantities in the order dL, m, resid, the wanted ones only)."""
+    bits = what if isinstance(what, int) else _curve_bits(what)
+    nq, w = bin(bits).count("1"), 2 + len(probs)
+    out, o = [], 0
+    for p in probs_list:
+        out.append(table[o:o + nq * p.N * w].reshape(nq, p.N, w))
+        o += nq * p.N * w
+    return out
+
+
+def curves_rows(block: np.ndarray, prob: ExpGPProblem, what, probs=DEFAULT_PROBS) -> dict:
+    """One group's block ``[nq, N, 2 + len(probs)]`` as ``{"dL": {"mean": [N], "sd": [N],
+    "2.5%": [N], ...}, "m": ..., "resid": ..., "x": x}``."""
+    bits = what if isinstance(what, int) else _curve_bits(what)
+    keys = ["mean", "sd"] + [f"{100 * p:g}%" for p in probs]
+    names = [n for n in CURVE_NAMES if bits & _lib.CURVE[n]]
+    rows = {n: {k: np.array(block[q, :, j]) for j, k in enumerate(keys)}
+            for q, n in enumerate(names)}
+    rows["x"] = prob.x.copy()
+    return rows
+
+
+def _curves_table(ps, what, c):
+    bits = what if isinstance(what, int) else _curve_bits(what)
+    nq = bin(bits).count("1") if 0 < bits < 8 else 3
+    return bits, np.empty(sum(p.N for p in ps) * nq * (2 + c.n_probs))
+
+
+def curves_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter: int = 0,
+                  probs=DEFAULT_PROBS, what=CURVE_NAMES, max_staging_bytes: int = 0,
+                  device: int = 0, stream: int = 0) -> np.ndarray:
+    """Posterior bands of the fitted curves of draws that lie in device memory
+    (``fitoct_curves_device``; ``d_draws``, ``prob`` as :func:`summary_device`): per depth bin
+    the mean, sd and quantiles of ``dL``, ``m`` and ``resid`` over the pooled post-warmup
+    draws.  Returns the packed table (blocks: :func:`curves_blocks`)."""
+    ps, arr = _problem_array(prob)
+    c = _summary_config(first_iter, probs, max_staging_bytes, device)
+    bits, out = _curves_table(ps, what, c)
+    check(lib().fitoct_curves_device(arr, len(ps), int(chains), int(iters_saved),
+                                     C.c_void_p(d_draws or None), bits, C.byref(c),
+                                     C.c_void_p(stream or None), dptr(out)))
+    return out
+
+
+def curves_host(draws: np.ndarray, prob, first_iter: int = 0, probs=DEFAULT_PROBS,
+                what=CURVE_NAMES) -> np.ndarray:
+    """The same table computed on the host (``fitoct_curves_host``) from raw draws
+    ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
+    ps, arr = _problem_array(prob)
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    if draws.ndim == 3:
+        draws = draws[None]
+    if draws.ndim != 4 or draws.shape[0] != len(ps):
+        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
+    if draws.shape[3] != ps[0].D + 8:
+        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    c = _summary_config(first_iter, probs)
+    bits, out = _curves_table(ps, what, c)
+    check(lib().fitoct_curves_host(arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws), bits,
+                                   C.byref(c), dptr(out)))
+    return out
+
+
+def _pick_indices(draws, n, seed, S):
+    """``generated_quantities``' selection: ``n`` of the S pooled draws at random, sorted, or
+    the explicit flat indices ``draws``."""
+    if draws is None:
+        rng = np.random.default_rng(seed)
+        draws = np.sort(rng.choice(S, size=min(n, S), replace=False))
+    return np.ascontiguousarray(draws, dtype=np.int64).reshape(-1)
+
+
+def _pick(prob, idx, call, call_params):
+    """The dict of ``generated_quantities`` from the two pick entries of a plan or a batch."""
+    k, N = idx.size, prob.N
+    mono = prob.prior_type == "monoexp"
+    dL, m, resid, br = np.empty((k, N)), np.empty((k, N)), np.empty((k, N)), np.empty(k)
+    theta, ygp = np.empty((k, 3)), np.zeros((k, 0 if mono else prob.Nn))
+    ip = idx.ctypes.data_as(_lib._lp)
+    check(call(k, ip, dptr(dL), dptr(m), dptr(resid), dptr(br)))
+    check(call_params(k, ip, dptr(theta), None if mono else dptr(ygp)))
+    return {"dL": dL, "m": m, "resid": resid, "br": br, "index": idx, "theta": theta, "yGP": ygp}
+
+
 MONITOR_KEYS = ("Rhat", "Rhat_bulk", "Rhat_fold", "Bulk_ESS", "Tail_ESS")
 
 
@@ -475,6 +575,33 @@ class Plan:
         check(lib().fitoct_plan_monitor(self._h, C.byref(c), dptr(out)))
         return monitor_rows(out, self.prob, pars)
 
+    def curves(self, what=CURVE_NAMES, probs=DEFAULT_PROBS, first_iter=None,
+               max_staging_bytes: int = 0) -> dict:
+        """Posterior bands of the fitted curves of the last run (plotExpGP's plot), computed on
+        the device from the draws where they lie: ``{"dL": {"mean": [N], "sd": [N], "2.5%":
+        [N], ...}, "m": ..., "resid": ..., "x": x}`` for the quantities named in ``what``.
+        ``first_iter`` defaults to the saved warmup."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        c = _summary_config(first_iter, probs, max_staging_bytes)
+        bits, out = _curves_table([self.prob], what, c)
+        check(lib().fitoct_plan_curves(self._h, bits, C.byref(c), dptr(out)))
+        return curves_rows(curves_blocks(out, [self.prob], bits, probs)[0], self.prob, bits, probs)
+
+    def curves_pick(self, draws=None, n=100, seed=None, first_iter=None) -> dict:
+        """:func:`fitoct_amd.genquant.generated_quantities` without the download: dict(index,
+        theta, yGP, dL, m, resid, br) of ``n`` post-warmup draws chosen at random (``seed``) or
+        of the flat indices ``draws`` (chain * n_post + iteration), evaluated on the device."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        S = self.info["chains"] * (self.info["iters_saved"] - first_iter)
+        idx = _pick_indices(draws, n, seed, S)
+        c = _summary_config(first_iter, ())
+        L, h = lib(), self._h
+        return _pick(self.prob, idx,
+                     lambda k, ip, *o: L.fitoct_plan_curves_pick(h, C.byref(c), k, ip, *o),
+                     lambda k, ip, *o: L.fitoct_plan_curves_pick_params(h, C.byref(c), k, ip, *o))
+
     def close(self):
         if getattr(self, "_h", None):
             lib().fitoct_plan_destroy(self._h)
@@ -570,6 +697,32 @@ class Batch:
         if problem is not None:
             return monitor_rows(out[problem], self.probs[problem], pars)
         return [monitor_rows(out[p], self.probs[p], pars) for p in range(len(self.probs))]
+
+    def curves(self, problem=None, what=CURVE_NAMES, probs=DEFAULT_PROBS, first_iter=None,
+               max_staging_bytes: int = 0):
+        """Posterior bands of the last run (:meth:`Plan.curves`) of every file in one call: a
+        list with one dict per problem, or problem ``problem``'s dict."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        c = _summary_config(first_iter, probs, max_staging_bytes)
+        bits, out = _curves_table(self.probs, what, c)
+        check(lib().fitoct_batch_curves(self._h, bits, C.byref(c), dptr(out)))
+        blocks = curves_blocks(out, self.probs, bits, probs)
+        if problem is not None:
+            return curves_rows(blocks[problem], self.probs[problem], bits, probs)
+        return [curves_rows(b, p, bits, probs) for b, p in zip(blocks, self.probs)]
+
+    def curves_pick(self, problem: int, draws=None, n=100, seed=None, first_iter=None) -> dict:
+        """:meth:`Plan.curves_pick` for problem ``problem`` of the last run."""
+        if first_iter is None:
+            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
+        S = self.cfg.chains * (self.info["iters_saved"] - first_iter)
+        idx = _pick_indices(draws, n, seed, S)
+        c = _summary_config(first_iter, ())
+        L, h, g = lib(), self._h, int(problem)
+        return _pick(self.probs[g], idx,
+                     lambda k, ip, *o: L.fitoct_batch_curves_pick(h, g, C.byref(c), k, ip, *o),
+                     lambda k, ip, *o: L.fitoct_batch_curves_pick_params(h, g, C.byref(c), k, ip, *o))
 
     def close(self):
         if getattr(self, "_h", None):

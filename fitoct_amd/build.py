@@ -48,6 +48,8 @@ SOURCES = [
     ("summary_device", "summary_device.hip", "hipcc", _KERNEL),
     # the rank diagnostics' kernels (the device sort) and entry points
     ("monitor_device", "monitor_device.hip", "hipcc", _KERNEL),
+    # the posterior curves' kernels and entry points
+    ("curves_device", "curves_device.hip", "hipcc", _KERNEL),
     ("fitoct_api", "fitoct_api.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("multi_device", "multi_device.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("host_model", "host_model.cpp", "g++", ["-O2", "-std=c++17"]),
@@ -57,7 +59,8 @@ SOURCES = [
     ("stamps_report", "stamps_report.cpp", "g++", ["-O2", "-std=c++17"]),
 ]
 # objects whose kernels' resource remarks are kept beside them (<object>.resources.txt)
-RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["summary_device", "monitor_device"]
+RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["summary_device", "monitor_device",
+                                                                         "curves_device"]
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")

@@ -319,6 +319,10 @@ int plan_common(fitoct_plan* pl, const fitoct_problem* p, int chains, int precis
     rc = build_basis(p, B, xg);
     if (rc) return rc;
   }
+  pl->h_xyu.assign(p->x, p->x + p->N);
+  pl->h_xyu.insert(pl->h_xyu.end(), p->y, p->y + p->N);
+  pl->h_xyu.insert(pl->h_xyu.end(), p->uy, p->uy + p->N);
+  pl->h_B = B;
   // basis mode (see kernel_params.h BasisMode)
   std::vector<double> ta, kinv, bv;
   int mode;

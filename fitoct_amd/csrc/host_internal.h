@@ -18,6 +18,12 @@ std::string column_name(int prior, int Nn, int i);
 int split_rhat_ess(const double* x, int chains, int n, double* rhat, double* ess);
 int rank_rhat(const double* x, int chains, int n, double* out);
 int monitor_column(const double* x, int chains, int n, double* out5);
+// Posterior curves of one group on the host (stan_output.cpp; include/fitoct.h "posterior
+// curves"): draws_g[chains][iters_saved][D + 8] raw rows, B the group's basis [N][Nn] (unused
+// for the mono-exponential model), out_g[nq][N][2 + n_probs].  Arguments already checked.
+int curves_host_group(const fitoct_problem* p, const double* B, int chains, int iters_saved,
+                      int first_iter, const double* draws_g, int what, int n_probs,
+                      const double* probs, double* out_g);
 bool log_transformed(int prior, int Nn, int j);
 void constrain(int prior, int Nn, const double* q, double* out);
 double lp_constant(const fitoct_problem* p);

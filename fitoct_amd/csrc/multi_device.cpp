@@ -211,6 +211,8 @@ int group_plan_create(const fitoct_problem* prob, const fitoct_config* cfg,
   const fitoct_plan* s0 = pl->shards[0];
   pl->cfg = *cfg;
   pl->prob = s0->prob;   // caller pointers already dropped
+  pl->h_xyu = s0->h_xyu;
+  pl->h_B = s0->h_B;
   pl->kp = s0->kp;
   pl->kp.chains = C;
   pl->kp.chain_offset = cfg->chain_offset;

@@ -65,6 +65,9 @@ struct fitoct_plan {
   int* h_cancel = nullptr;    // host-pinned flag polled by the kernel
   long long* d_stamps = nullptr;   // diagnostic stamps of the launch in flight
   fitoct::PairBuffers pairs;       // paired tiles (sched.pair)
+  // the plan's own host copies of x | y | uy and of the basis rows [N][Nn] (empty for the
+  // mono-exponential model): what the posterior curves read of the problem (curves_device.hip)
+  std::vector<double> h_xyu, h_B;
 
   // ---- multi-device plan (cfg.n_devices > 1; multi_device.cpp) ----
   // One single-device plan per device; shard r runs this plan's chains

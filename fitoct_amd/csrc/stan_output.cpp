@@ -1,6 +1,7 @@
 // Stan-format output of libfitoct (host only): the column layout the reference's
-// consumers read, generated quantities per bin, and the one Stan-CSV writer that
-// both bindings (the R .Call shim and the Python ctypes mirror) use.
+// consumers read, generated quantities per bin (for given rows, and as posterior bands over
+// a group's pooled draws: the host route of the posterior curves), and the one Stan-CSV writer
+// that both bindings (the R .Call shim and the Python ctypes mirror) use.
 //
 // Consumers (SURVEY.md §8b "R return value"): plotExpGP.R:9,41-43 and
 // server.R:88-237 ask for pars = c('theta','yGP','lambda','sigma','br','lp__')
@@ -112,6 +113,86 @@ void write_header_tail(FILE* f, const fitoct_problem* p, long long id, unsigned 
 }
 
 }  // namespace
+
+// ---- posterior curves on the host (include/fitoct.h "posterior curves") -----------------------
+// Bin-major over the group's pooled draws: per bin the values of every draw (curve_bin), then
+// per wanted quantity the pooled mean and sd and the order statistics by std::nth_element on
+// order_keys, as the summary's host route does.
+int curves_host_group(const fitoct_problem* p, const double* B, int chains, int iters_saved,
+                      int first_iter, const double* draws_g, int what, int n_probs,
+                      const double* probs, double* out_g) {
+  const OutModel om = out_model(p);
+  const bool mono = p->prior_type == FITOCT_MODEL_MONOEXP;
+  const int N = p->N, nn = mono ? 0 : p->Nn, np_ = 3 + nn, width = 2 + n_probs;
+  const int n = iters_saved - first_iter, W = om.D + 8;
+  const int64_t S = (int64_t)chains * n;
+  int nq = 0;
+  for (int b = 0; b < 3; ++b) nq += (what >> b) & 1;
+  // theta and yGP of every pooled draw, chain-major, in the OUTPUT layout's values
+  std::vector<double> pm((size_t)S * np_);
+  bool group_nan = false;
+  for (int c = 0; c < chains; ++c)
+    for (int i = 0; i < n; ++i) {
+      const double* raw = draws_g + ((size_t)c * iters_saved + first_iter + i) * W + 7;
+      double* o = pm.data() + ((size_t)c * n + i) * np_;
+      for (int k = 0; k < np_; ++k) {
+        o[k] = out_value(om, curve_param_spec(om, k), raw);
+        group_nan = group_nan || o[k] != o[k];
+      }
+    }
+  if (group_nan) {   // a NaN in any theta or yGP draw blanks the group
+    std::fill(out_g, out_g + (size_t)nq * N * width, NAN);
+    return FITOCT_OK;
+  }
+  std::vector<QIndex> qidx(n_probs);
+  for (int i = 0; i < n_probs; ++i) qidx[i] = quantile_index(S, probs[i]);
+  std::vector<double> val[3];
+  for (int b = 0; b < 3; ++b)
+    if ((what >> b) & 1) val[b].resize((size_t)S);
+  std::vector<uint64_t> keys((size_t)S);
+  const double c = (double)p->data_type;
+  for (int i = 0; i < N; ++i) {
+    for (int64_t s = 0; s < S; ++s) {
+      const double* r = pm.data() + (size_t)s * np_;
+      const CurveBin v = curve_bin(B + (size_t)i * nn, nn, r + 3, r, -c * p->x[i], p->y[i], p->uy[i]);
+      if (what & FITOCT_CURVE_DL) val[0][s] = v.dL;
+      if (what & FITOCT_CURVE_M) val[1][s] = v.m;
+      if (what & FITOCT_CURVE_RESID) val[2][s] = v.resid;
+    }
+    int q = 0;
+    for (int b = 0; b < 3; ++b) {
+      if (!((what >> b) & 1)) continue;
+      double* row = out_g + ((size_t)(q++) * N + i) * width;
+      const std::vector<double>& x = val[b];
+      bool has_nan = false;
+      double sum = 0.0, ssq = 0.0;
+      for (int64_t s = 0; s < S; ++s) {
+        has_nan = has_nan || x[s] != x[s];
+        sum += x[s];
+      }
+      if (has_nan) {
+        std::fill(row, row + width, NAN);
+        continue;
+      }
+      const double mean = sum / (double)S;
+      for (int64_t s = 0; s < S; ++s) ssq += (x[s] - mean) * (x[s] - mean);
+      row[0] = mean;
+      row[1] = sqrt(ssq / (double)(S - 1));
+      if (n_probs > 0)
+        for (int64_t s = 0; s < S; ++s) keys[s] = order_key(x[s]);
+      for (int j = 0; j < n_probs; ++j) {
+        std::nth_element(keys.begin(), keys.begin() + qidx[j].lo, keys.end());
+        const double x_lo = key_value(keys[qidx[j].lo]);
+        const double x_hi = qidx[j].hi > qidx[j].lo
+                                ? key_value(*std::min_element(keys.begin() + qidx[j].hi, keys.end()))
+                                : x_lo;
+        row[2 + j] = quantile_lerp(x_lo, x_hi, qidx[j].frac);
+      }
+    }
+  }
+  return FITOCT_OK;
+}
+
 }  // namespace fitoct
 
 using namespace fitoct;
@@ -323,16 +404,13 @@ int32_t fitoct_expgp_curves(const fitoct_problem* prob, int32_t n, const double*
       const double* th = theta + (size_t)s * 3;
       double acc = 0.0;
       for (int i = 0; i < N; ++i) {
-        double d = 0.0;   // dL_i = B_i . yGP   
-        for (int k = 0; k < Nn; ++k) d += B[(size_t)i * Nn + k] * ygp[(size_t)s * Nn + k];
-        // m_i = theta1 + theta2 exp(-c x_i / (theta3 (1 + dL_i)))   (ui.R:88, synthData.R:22)
-        const double mi = th[0] + th[1] * exp(-c * prob->x[i] / (th[2] * (1.0 + d)));
-        const double ri = (prob->y[i] - mi) / prob->uy[i];
-        acc += ri * ri;
+        const CurveBin v = curve_bin(B.data() + (size_t)i * Nn, Nn, ygp + (size_t)s * Nn, th,
+                                     -c * prob->x[i], prob->y[i], prob->uy[i]);
+        acc += v.resid * v.resid;
         const size_t o = (size_t)s * N + i;
-        if (dL) dL[o] = d;
-        if (m) m[o] = mi;
-        if (resid) resid[o] = ri;
+        if (dL) dL[o] = v.dL;
+        if (m) m[o] = v.m;
+        if (resid) resid[o] = v.resid;
       }
       if (br) br[s] = acc / N;
     }

@@ -39,10 +39,6 @@
 namespace fitoct {
 namespace {
 
-constexpr int QT_MAX = 2 * MAX_PROBS;   // order statistics per column: x[lo], x[hi] per probability
-constexpr int QHIST_THREADS = 256;
-constexpr int QHIST_PER_THREAD = 16;    // elements per thread and grid stride
-
 // out row = mean, se_mean, sd, the quantiles, n_eff, Rhat
 void put_row(const Shape& s, double* row, double mean, double sd, const double* q, double ess,
              double rhat) {
@@ -107,80 +103,8 @@ int summary_host(const Shape& s, const double* draws, const fitoct_summary_confi
   return FITOCT_OK;
 }
 
-// ---- kernels (stage_kernel, moments_kernel, acov_kernel: summary_kernels.h) ------------------
-// Radix-select state of one pair: T targets (order statistics), each with the key prefix found
-// so far, its rank among the keys sharing that prefix, and the histogram slot of its prefix
-// (targets with equal prefixes share one).
-struct QState {
-  int T;
-  int64_t S;
-  unsigned long long* hist;   // [pairs][QT_MAX][256]
-  long long* rank;            // [pairs][QT_MAX]
-  unsigned long long* pre;    // [pairs][QT_MAX] prefix of each target
-  int* slot;                  // [pairs][QT_MAX]
-  unsigned long long* uniq;   // [pairs][QT_MAX] distinct prefixes
-  int* nuniq;                 // [pairs]
-};
-
-// digits of byte `pass` (0 = most significant) of the keys whose higher bytes equal a prefix
-__global__ __launch_bounds__(QHIST_THREADS) void qhist_kernel(const double* X, QState q, int pass,
-                                                              int nblk) {
-  __shared__ unsigned int lh[QT_MAX * 256];
-  __shared__ unsigned long long spre[QT_MAX];
-  const int64_t pair = blockIdx.x / nblk;
-  const int blk = blockIdx.x % nblk;
-  const int U = q.nuniq[pair];
-  for (int t = threadIdx.x; t < U * 256; t += QHIST_THREADS) lh[t] = 0u;
-  if ((int)threadIdx.x < U) spre[threadIdx.x] = q.uniq[pair * QT_MAX + threadIdx.x];
-  __syncthreads();
-  const double* x = X + (size_t)pair * q.S;
-  const int shift = 56 - 8 * pass;
-  for (int64_t i = (int64_t)blk * QHIST_THREADS + threadIdx.x; i < q.S;
-       i += (int64_t)nblk * QHIST_THREADS) {
-    const unsigned long long key = order_key(x[i]);
-    const unsigned int digit = (unsigned int)(key >> shift) & 255u;
-    const unsigned long long hi = pass == 0 ? 0ull : key >> (shift + 8);
-    for (int u = 0; u < U; ++u)
-      if (hi == spre[u]) atomicAdd(&lh[u * 256 + digit], 1u);
-  }
-  __syncthreads();
-  unsigned long long* H = q.hist + (size_t)pair * QT_MAX * 256;
-  for (int t = threadIdx.x; t < U * 256; t += QHIST_THREADS)
-    if (lh[t]) atomicAdd(&H[t], (unsigned long long)lh[t]);
-}
-
-// one wave per pair: each target walks its histogram to its digit; then the distinct prefixes
-// are renumbered and the histograms cleared for the next pass
-__global__ __launch_bounds__(64) void qselect_kernel(QState q) {
-  const int64_t pair = blockIdx.x;
-  unsigned long long* H = q.hist + (size_t)pair * QT_MAX * 256;
-  const int t = threadIdx.x;
-  if (t < q.T) {
-    const unsigned long long* h = H + (size_t)q.slot[pair * QT_MAX + t] * 256;
-    long long r = q.rank[pair * QT_MAX + t], cum = 0;
-    int d = 0;
-    for (; d < 255; ++d) {
-      const long long c = (long long)h[d];
-      if (r < cum + c) break;
-      cum += c;
-    }
-    q.rank[pair * QT_MAX + t] = r - cum;
-    q.pre[pair * QT_MAX + t] = (q.pre[pair * QT_MAX + t] << 8) | (unsigned long long)d;
-  }
-  __syncthreads();
-  if (t == 0) {
-    int U = 0;
-    for (int a = 0; a < q.T; ++a) {
-      const unsigned long long p = q.pre[pair * QT_MAX + a];
-      int u = 0;
-      while (u < U && q.uniq[pair * QT_MAX + u] != p) ++u;
-      if (u == U) q.uniq[pair * QT_MAX + U++] = p;
-      q.slot[pair * QT_MAX + a] = u;
-    }
-    q.nuniq[pair] = U;
-  }
-  for (int i = t; i < QT_MAX * 256; i += 64) H[i] = 0ull;
-}
+// ---- kernels: stage_kernel, moments_kernel, acov_kernel, qhist_kernel, qselect_kernel
+// (summary_kernels.h, shared with monitor_device.hip and curves_device.hip) ------------------
 
 // ---- device route ---------------------------------------------------------------------------
 int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_config* cfg,
@@ -191,41 +115,26 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
   const int ncc_max = columns_per_pass(s, cfg, col_bytes);
   const int64_t pairs_max = (int64_t)s.G * ncc_max;
   const int rblocks = (s.n + STAGE_ROWS - 1) / STAGE_ROWS;
-  const int nblk = (int)std::max<int64_t>(
-      1, std::min<int64_t>(1024, (s.S + QHIST_THREADS * QHIST_PER_THREAD - 1) /
-                                     (QHIST_THREADS * QHIST_PER_THREAD)));
+  const int nblk = qhist_blocks(s.S);
   const int64_t limit = (int64_t)1 << 31;
   if ((int64_t)rblocks * s.C * s.G >= limit || pairs_max * s.m >= limit ||
       pairs_max * nblk >= limit)
     return fail(FITOCT_E_ARG, "summary: shape too large for one launch (lower max_staging_bytes)");
   const int T = 2 * s.np;
 
-  DevBuf X, lscale, hist, rank, pre, slot, uniq, nuniq;
+  DevBuf X, lscale;
   EssBufs eb;
+  SelectBufs sel;
   FITOCT_TRY(X.alloc((size_t)pairs_max * s.S * sizeof(double)));
   FITOCT_TRY(eb.alloc(pairs_max, s.m));
   FITOCT_TRY(lscale.alloc((size_t)s.G * sizeof(double)));
-  if (T > 0) {
-    FITOCT_TRY(hist.alloc((size_t)pairs_max * QT_MAX * 256 * sizeof(unsigned long long)));
-    FITOCT_TRY(rank.alloc((size_t)pairs_max * QT_MAX * sizeof(long long)));
-    FITOCT_TRY(pre.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
-    FITOCT_TRY(slot.alloc((size_t)pairs_max * QT_MAX * sizeof(int)));
-    FITOCT_TRY(uniq.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
-    FITOCT_TRY(nuniq.alloc((size_t)pairs_max * sizeof(int)));
-  }
+  if (T > 0) FITOCT_TRY(sel.alloc(pairs_max));
   HIP_TRY(hipMemcpyAsync(lscale.p, s.lscale.data(), sizeof(double) * s.G, hipMemcpyHostToDevice, st));
 
   // the order statistics every column needs: x[lo], x[hi] of each probability
   std::vector<QIndex> qidx(s.np);
-  std::vector<long long> rank0((size_t)pairs_max * QT_MAX, 0);
-  std::vector<int> one((size_t)pairs_max, 1);
-  for (int i = 0; i < s.np; ++i) {
-    qidx[i] = quantile_index(s.S, cfg->probs[i]);
-    for (int64_t p = 0; p < pairs_max; ++p) {
-      rank0[p * QT_MAX + 2 * i] = qidx[i].lo;
-      rank0[p * QT_MAX + 2 * i + 1] = qidx[i].hi;
-    }
-  }
+  for (int i = 0; i < s.np; ++i) qidx[i] = quantile_index(s.S, cfg->probs[i]);
+  const SelectRanks ranks(qidx, pairs_max);
 
   std::vector<double> h_mom, cm(s.m), cv(s.m), q((size_t)std::max(1, s.np));
   std::vector<int> h_flags;
@@ -241,29 +150,7 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
     FITOCT_TRY(queue_moments(k, X.as<double>(), pairs, eb, st, h_mom, h_flags));
 
     // quantiles: queued behind the moments, read back after the autocovariance rounds
-    if (T > 0) {
-      QState qs{T, s.S, hist.as<unsigned long long>(), rank.as<long long>(),
-                pre.as<unsigned long long>(), slot.as<int>(), uniq.as<unsigned long long>(),
-                nuniq.as<int>()};
-      HIP_TRY(hipMemsetAsync(hist.p, 0, (size_t)pairs * QT_MAX * 256 * sizeof(unsigned long long), st));
-      HIP_TRY(hipMemsetAsync(pre.p, 0, (size_t)pairs * QT_MAX * sizeof(unsigned long long), st));
-      HIP_TRY(hipMemsetAsync(slot.p, 0, (size_t)pairs * QT_MAX * sizeof(int), st));
-      HIP_TRY(hipMemsetAsync(uniq.p, 0, (size_t)pairs * QT_MAX * sizeof(unsigned long long), st));
-      HIP_TRY(hipMemcpyAsync(rank.p, rank0.data(), (size_t)pairs * QT_MAX * sizeof(long long),
-                             hipMemcpyHostToDevice, st));
-      HIP_TRY(hipMemcpyAsync(nuniq.p, one.data(), (size_t)pairs * sizeof(int),
-                             hipMemcpyHostToDevice, st));
-      for (int pass = 0; pass < 8; ++pass) {
-        qhist_kernel<<<dim3((unsigned)(pairs * nblk)), dim3(QHIST_THREADS), 0, st>>>(
-            X.as<double>(), qs, pass, nblk);
-        HIP_TRY(hipGetLastError());
-        qselect_kernel<<<dim3((unsigned)pairs), dim3(64), 0, st>>>(qs);
-        HIP_TRY(hipGetLastError());
-      }
-      h_keys.resize((size_t)pairs * QT_MAX);
-      HIP_TRY(hipMemcpyAsync(h_keys.data(), pre.p, sizeof(unsigned long long) * h_keys.size(),
-                             hipMemcpyDeviceToHost, st));
-    }
+    if (T > 0) FITOCT_TRY(queue_select(X.as<double>(), pairs, s.S, T, nblk, sel, ranks, st, h_keys));
     HIP_TRY(hipStreamSynchronize(st));
 
     // per pair: NaN / constant pattern, pooled mean and sd, Rhat; which pairs need n_eff
@@ -281,23 +168,7 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
       c.has_nan = fl & 1;
       c.constant = !(fl & 2);
       if (c.has_nan) continue;
-      double sum = 0.0;
-      for (int j = 0; j < s.m; ++j) sum += mo[4 * j + 2];
-      if (s.n & 1)
-        for (int j = 0; j < s.m; j += 2) sum += mo[4 * j + 3];
-      c.mean = sum / (double)s.S;
-      // pooled centred sum of squares from the split chains' own (Chan et al.'s update)
-      double ssq = 0.0;
-      for (int j = 0; j < s.m; ++j) {
-        const double d = mo[4 * j] - c.mean;
-        ssq += mo[4 * j + 1] + s.h * (d * d);
-      }
-      if (s.n & 1)
-        for (int j = 0; j < s.m; j += 2) {
-          const double d = mo[4 * j + 3] - c.mean;
-          ssq += d * d;
-        }
-      c.sd = sqrt(ssq / (double)(s.S - 1));
+      pooled_mean_sd(mo, s.n, s.h, s.m, s.S, c.mean, c.sd);
       if (c.constant) continue;   // n_eff and Rhat are NaN (split_rhat_ess)
       for (int j = 0; j < s.m; ++j) {
         cm[j] = mo[4 * j];

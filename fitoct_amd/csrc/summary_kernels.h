@@ -1,9 +1,10 @@
-// What the device routes of the posterior summary (summary_device.hip) and of the rank
-// diagnostics (monitor_device.hip) share: the argument checks and the
-// shape arithmetic, the staging, moments and autocovariance kernels, the device buffers, the
-// split of the output columns into passes, and the rounds of Geyer's rule over lag blocks.
-// Included by those two translation units only; everything has internal linkage, so each
-// object carries its own copy of the kernels.
+// What the device routes of the posterior summary (summary_device.hip), of the rank
+// diagnostics (monitor_device.hip) and of the posterior curves (curves_device.hip) share
+// (DESIGN.md §4): the argument checks and the shape arithmetic, the staging, moments and
+// autocovariance kernels, the exact radix select of the quantiles with its set-up, the device
+// buffers, the split of the output columns into passes, and the rounds of Geyer's rule over
+// lag blocks.  Included by those translation units only; everything has internal linkage, so
+// each object carries its own copy of the kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,9 @@ constexpr int STAGE_ROWS = 32;          // rows of one chain per stage_kernel wo
 constexpr int STAGE_THREADS = 256;
 constexpr int ACOV_WAVES = 4;
 constexpr int ACOV_TILE = 512;          // series elements per LDS tile and wave
+constexpr int QT_MAX = 2 * MAX_PROBS;   // order statistics per column: x[lo], x[hi] per probability
+constexpr int QHIST_THREADS = 256;
+constexpr int QHIST_PER_THREAD = 16;    // elements per thread and grid stride
 
 // What a call computes: shapes checked by check_args.
 struct Shape {
@@ -239,6 +243,80 @@ __global__ __launch_bounds__(ACOV_WAVES * 64) void acov_kernel(KShape k, const d
   }
 }
 
+// Radix-select state of one pair: T targets (order statistics), each with the key prefix found
+// so far, its rank among the keys sharing that prefix, and the histogram slot of its prefix
+// (targets with equal prefixes share one).
+struct QState {
+  int T;
+  int64_t S;
+  unsigned long long* hist;   // [pairs][QT_MAX][256]
+  long long* rank;            // [pairs][QT_MAX]
+  unsigned long long* pre;    // [pairs][QT_MAX] prefix of each target
+  int* slot;                  // [pairs][QT_MAX]
+  unsigned long long* uniq;   // [pairs][QT_MAX] distinct prefixes
+  int* nuniq;                 // [pairs]
+};
+
+// digits of byte `pass` (0 = most significant) of the keys whose higher bytes equal a prefix
+__global__ __launch_bounds__(QHIST_THREADS) void qhist_kernel(const double* X, QState q, int pass,
+                                                              int nblk) {
+  __shared__ unsigned int lh[QT_MAX * 256];
+  __shared__ unsigned long long spre[QT_MAX];
+  const int64_t pair = blockIdx.x / nblk;
+  const int blk = blockIdx.x % nblk;
+  const int U = q.nuniq[pair];
+  for (int t = threadIdx.x; t < U * 256; t += QHIST_THREADS) lh[t] = 0u;
+  if ((int)threadIdx.x < U) spre[threadIdx.x] = q.uniq[pair * QT_MAX + threadIdx.x];
+  __syncthreads();
+  const double* x = X + (size_t)pair * q.S;
+  const int shift = 56 - 8 * pass;
+  for (int64_t i = (int64_t)blk * QHIST_THREADS + threadIdx.x; i < q.S;
+       i += (int64_t)nblk * QHIST_THREADS) {
+    const unsigned long long key = order_key(x[i]);
+    const unsigned int digit = (unsigned int)(key >> shift) & 255u;
+    const unsigned long long hi = pass == 0 ? 0ull : key >> (shift + 8);
+    for (int u = 0; u < U; ++u)
+      if (hi == spre[u]) atomicAdd(&lh[u * 256 + digit], 1u);
+  }
+  __syncthreads();
+  unsigned long long* H = q.hist + (size_t)pair * QT_MAX * 256;
+  for (int t = threadIdx.x; t < U * 256; t += QHIST_THREADS)
+    if (lh[t]) atomicAdd(&H[t], (unsigned long long)lh[t]);
+}
+
+// one wave per pair: each target walks its histogram to its digit; then the distinct prefixes
+// are renumbered and the histograms cleared for the next pass
+__global__ __launch_bounds__(64) void qselect_kernel(QState q) {
+  const int64_t pair = blockIdx.x;
+  unsigned long long* H = q.hist + (size_t)pair * QT_MAX * 256;
+  const int t = threadIdx.x;
+  if (t < q.T) {
+    const unsigned long long* h = H + (size_t)q.slot[pair * QT_MAX + t] * 256;
+    long long r = q.rank[pair * QT_MAX + t], cum = 0;
+    int d = 0;
+    for (; d < 255; ++d) {
+      const long long c = (long long)h[d];
+      if (r < cum + c) break;
+      cum += c;
+    }
+    q.rank[pair * QT_MAX + t] = r - cum;
+    q.pre[pair * QT_MAX + t] = (q.pre[pair * QT_MAX + t] << 8) | (unsigned long long)d;
+  }
+  __syncthreads();
+  if (t == 0) {
+    int U = 0;
+    for (int a = 0; a < q.T; ++a) {
+      const unsigned long long p = q.pre[pair * QT_MAX + a];
+      int u = 0;
+      while (u < U && q.uniq[pair * QT_MAX + u] != p) ++u;
+      if (u == U) q.uniq[pair * QT_MAX + U++] = p;
+      q.slot[pair * QT_MAX + a] = u;
+    }
+    q.nuniq[pair] = U;
+  }
+  for (int i = t; i < QT_MAX * 256; i += 64) H[i] = 0ull;
+}
+
 // ---- device route ---------------------------------------------------------------------------
 struct DevBuf {
   void* p = nullptr;
@@ -307,6 +385,30 @@ inline int queue_moments(const KShape& k, const double* X, int64_t pairs, EssBuf
   return FITOCT_OK;
 }
 
+// Pooled mean and sd (n - 1) of one pair from the moments of its m split chains of h draws
+// (moments_kernel's rows mo[m][4]; S = m / 2 * n values): the sums are added in chain order,
+// the centred sums of squares combined by Chan et al.'s update; the middle draw of an odd n
+// is carried separately.
+inline void pooled_mean_sd(const double* mo, int n, int h, int m, int64_t S, double& mean,
+                           double& sd) {
+  double sum = 0.0;
+  for (int j = 0; j < m; ++j) sum += mo[4 * j + 2];
+  if (n & 1)
+    for (int j = 0; j < m; j += 2) sum += mo[4 * j + 3];
+  mean = sum / (double)S;
+  double ssq = 0.0;
+  for (int j = 0; j < m; ++j) {
+    const double d = mo[4 * j] - mean;
+    ssq += mo[4 * j + 1] + h * (d * d);
+  }
+  if (n & 1)
+    for (int j = 0; j < m; j += 2) {
+      const double d = mo[4 * j + 3] - mean;
+      ssq += d * d;
+    }
+  sd = sqrt(ssq / (double)(S - 1));
+}
+
 // n_eff of the pairs listed in `active` (ess[pair] is written): autocovariance in blocks of 64
 // lags, Geyer's rule (ess_moments) on the host block by block, the next block only for the
 // pairs that have not terminated.  h_mom: the moments of X (queue_moments, synchronised), still
@@ -351,6 +453,68 @@ inline int ess_rounds(const KShape& k, const double* X, EssBufs& b, hipStream_t 
     active.swap(still);
     slot.swap(still_slot);
   }
+  return FITOCT_OK;
+}
+
+// ---- exact radix select (qhist_kernel / qselect_kernel) -------------------------------------
+// Device buffers of the select, for up to pairs_max pairs.
+struct SelectBufs {
+  DevBuf hist, rank, pre, slot, uniq, nuniq;
+  int alloc(int64_t pairs_max) {
+    FITOCT_TRY(hist.alloc((size_t)pairs_max * QT_MAX * 256 * sizeof(unsigned long long)));
+    FITOCT_TRY(rank.alloc((size_t)pairs_max * QT_MAX * sizeof(long long)));
+    FITOCT_TRY(pre.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
+    FITOCT_TRY(slot.alloc((size_t)pairs_max * QT_MAX * sizeof(int)));
+    FITOCT_TRY(uniq.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
+    FITOCT_TRY(nuniq.alloc((size_t)pairs_max * sizeof(int)));
+    return FITOCT_OK;
+  }
+};
+// The order statistics every pair needs, x[lo] and x[hi] of each probability, as the initial
+// ranks of up to pairs_max pairs (and the one distinct prefix every pair starts with).
+struct SelectRanks {
+  std::vector<long long> rank0;
+  std::vector<int> one;
+  SelectRanks(const std::vector<QIndex>& qidx, int64_t pairs_max)
+      : rank0((size_t)pairs_max * QT_MAX, 0), one((size_t)pairs_max, 1) {
+    for (size_t i = 0; i < qidx.size(); ++i)
+      for (int64_t p = 0; p < pairs_max; ++p) {
+        rank0[p * QT_MAX + 2 * i] = qidx[i].lo;
+        rank0[p * QT_MAX + 2 * i + 1] = qidx[i].hi;
+      }
+  }
+};
+// workgroups of qhist_kernel per pair
+inline int qhist_blocks(int64_t S) {
+  return (int)std::max<int64_t>(
+      1, std::min<int64_t>(1024, (S + QHIST_THREADS * QHIST_PER_THREAD - 1) /
+                                     (QHIST_THREADS * QHIST_PER_THREAD)));
+}
+// The eight passes over X[pairs][S] for T targets per pair and the read-back of the selected
+// keys h_keys[pairs][QT_MAX], queued on st (not synchronised).
+inline int queue_select(const double* X, int64_t pairs, int64_t S, int T, int nblk,
+                        const SelectBufs& b, const SelectRanks& r, hipStream_t st,
+                        std::vector<unsigned long long>& h_keys) {
+  QState qs{T, S, b.hist.as<unsigned long long>(), b.rank.as<long long>(),
+            b.pre.as<unsigned long long>(), b.slot.as<int>(), b.uniq.as<unsigned long long>(),
+            b.nuniq.as<int>()};
+  HIP_TRY(hipMemsetAsync(b.hist.p, 0, (size_t)pairs * QT_MAX * 256 * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(b.pre.p, 0, (size_t)pairs * QT_MAX * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemsetAsync(b.slot.p, 0, (size_t)pairs * QT_MAX * sizeof(int), st));
+  HIP_TRY(hipMemsetAsync(b.uniq.p, 0, (size_t)pairs * QT_MAX * sizeof(unsigned long long), st));
+  HIP_TRY(hipMemcpyAsync(b.rank.p, r.rank0.data(), (size_t)pairs * QT_MAX * sizeof(long long),
+                         hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b.nuniq.p, r.one.data(), (size_t)pairs * sizeof(int),
+                         hipMemcpyHostToDevice, st));
+  for (int pass = 0; pass < 8; ++pass) {
+    qhist_kernel<<<dim3((unsigned)(pairs * nblk)), dim3(QHIST_THREADS), 0, st>>>(X, qs, pass, nblk);
+    HIP_TRY(hipGetLastError());
+    qselect_kernel<<<dim3((unsigned)pairs), dim3(64), 0, st>>>(qs);
+    HIP_TRY(hipGetLastError());
+  }
+  h_keys.resize((size_t)pairs * QT_MAX);
+  HIP_TRY(hipMemcpyAsync(h_keys.data(), b.pre.p, sizeof(unsigned long long) * h_keys.size(),
+                         hipMemcpyDeviceToHost, st));
   return FITOCT_OK;
 }
 

@@ -82,6 +82,28 @@ FITOCT_HD inline double out_value(const OutModel& m, OutSpec c, const double* r)
   }
 }
 
+// ---- fitted curves (fitoct_expgp_curves, fitoct_curves_*: "posterior curves") -----------------
+// Curve parameter k of a draw: theta.1..3 (k < 3), then yGP.(k - 2), as OUTPUT-layout columns.
+FITOCT_HD inline OutSpec curve_param_spec(const OutModel& m, int k) {
+  if (k < 3 || m.fam != FITOCT_PRIOR_HORSESHOE) return {S_RAW, k};
+  return {S_HS_YGP, k - 3};
+}
+// One bin of one draw: dL_i = B_i . yGP,
+// m_i = theta1 + theta2 exp(-c x_i / (theta3 (1 + dL_i))) (ui.R:88, synthData.R:22),
+// resid_i = (y_i - m_i) / uy_i.  ncx = -c x_i; nn = 0 for the mono-exponential model.  The
+// one copy of the loop body: the host routes and the device kernels differ only in exp and in
+// the fma contraction of the device compile.
+struct CurveBin {
+  double dL, m, resid;
+};
+FITOCT_HD inline CurveBin curve_bin(const double* Brow, int nn, const double* ygp,
+                                    const double* th, double ncx, double y, double uy) {
+  double d = 0.0;
+  for (int k = 0; k < nn; ++k) d += Brow[k] * ygp[k];
+  const double mi = th[0] + th[1] * exp(ncx / (th[2] * (1.0 + d)));
+  return {d, mi, (y - mi) / uy};
+}
+
 // ---- quantiles ----------------------------------------------------------------------------
 // Order-preserving 64-bit key of a double: key(a) < key(b) as unsigned integers where a < b,
 // with -0.0 below +0.0 (a total order, so that an order statistic is one bit pattern).

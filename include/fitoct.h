@@ -19,6 +19,9 @@
  *                              quantiles, n_eff, Rhat) of draws that stay in HBM
  *   fitoct_monitor_*()      <- rstan::monitor's rank-normalised Rhat, Bulk_ESS and Tail_ESS of
  *                              the same draws
+ *   fitoct_curves_*()       <- the fit's plot (plotExpGP.R:52-58, server.R:494-501): posterior
+ *                              bands of dL, m and the residuals per depth bin, and the curves of
+ *                              picked draws, of the same draws
  *   fitoct_plan_*()         <- same as fitoct_expgp_sample, split so that inputs can stay
  *                              resident in HBM across calls and draws can land in a
  *                              caller-owned device buffer (multi-GPU gather / benchmarking)
@@ -574,6 +577,76 @@ int32_t fitoct_monitor_host(const fitoct_problem* probs, int32_t n_groups, int32
                             const fitoct_summary_config* cfg, double* out);
 int32_t fitoct_plan_monitor(fitoct_plan* plan, const fitoct_summary_config* cfg, double* out);
 int32_t fitoct_batch_monitor(fitoct_batch* batch, const fitoct_summary_config* cfg, double* out);
+
+/* ---- posterior curves (added within ABI 8: new entries only, no struct above changed) ------- *
+ * The plot of the fit (plotExpGP.R:52-58, server.R:494-501) from draws that stay in HBM: per
+ * depth bin i the band of the decay-length modulation dL_i = B_i . yGP, of the model curve
+ * m_i = theta1 + theta2 exp(-c x_i / (theta3 (1 + dL_i))) and of the normalised residuals
+ * resid_i = (y_i - m_i) / uy_i (fitoct_expgp_curves' definitions), over the
+ * S = chains (iters_saved - first_iter) post-warmup draws pooled over chains.  A row is
+ * mean, sd (n - 1), then the type-7 quantiles at cfg->probs (the summary's arithmetic); there
+ * is no n_eff / Rhat per bin.  theta and yGP are the OUTPUT-layout columns theta.k / yGP.k
+ * (horseshoe: yGP = z lambda tau, the summary's bits); FITOCT_MODEL_MONOEXP has no yGP: its dL
+ * is 0 for every draw.  The problems must carry x, y, uy and N; the basis is prob->B or built
+ * as fitoct_build_basis does.
+ * `what` is a set of FITOCT_CURVE_* bits, nq of them.  The output is packed: group g's block
+ * is [nq][N_g][2 + n_probs], quantities in the order dL, m, resid (the wanted ones only);
+ * the groups' blocks follow one another (N may differ between groups).  A (group, quantity,
+ * bin) whose values hold a NaN gives an all-NaN row; a NaN in any theta or yGP draw of a group
+ * blanks that group and no other.  Infinite values are ordinary values of the total order.
+ * cfg is the summary's: first_iter, n_probs, probs, max_staging_bytes, device.  The device
+ * route evaluates as many (group, quantity, bin) series of S doubles per pass as
+ * max_staging_bytes holds (never fewer than one, never more than 4096: the quantile select
+ * keeps 64 KiB of histograms per series); its compact copy of theta and yGP,
+ * n_groups * S * (3 + Nn) doubles (151 MB at 1024 chains x 1000 draws, Nn = 15), lies outside
+ * that cap.  Results are the same bit for bit from call to call and for any max_staging_bytes.
+ * Refusals, all before the first HIP call: the summary's, and FITOCT_E_ARG for `what` 0 or
+ * with unknown bits, x, y or uy NULL, N < 2, fewer than 2 pooled draws. */
+#define FITOCT_CURVE_DL 1
+#define FITOCT_CURVE_M 2
+#define FITOCT_CURVE_RESID 4
+int32_t fitoct_curves_width(int32_t n_probs);                  /* 2 + n_probs */
+int32_t fitoct_curves_device(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                             int32_t iters_saved, const void* d_draws, int32_t what,
+                             const fitoct_summary_config* cfg, void* stream, double* out);
+/* the same computation on the host (draws: a host buffer; cfg->device and max_staging_bytes
+ * are ignored): the reference the device route is tested against */
+int32_t fitoct_curves_host(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                           int32_t iters_saved, const double* draws, int32_t what,
+                           const fitoct_summary_config* cfg, double* out);
+/* Bands of the last completed run's draws where they lie; refused exactly where
+ * fitoct_plan_summary / fitoct_batch_summary are (before a run, while a launch is in flight,
+ * device-list shards left in per-device buffers).  The plan (batch) keeps its own copy of x,
+ * y, uy and the basis.  out as above (cfg->device is ignored). */
+int32_t fitoct_plan_curves(fitoct_plan* plan, int32_t what, const fitoct_summary_config* cfg,
+                           double* out);
+int32_t fitoct_batch_curves(fitoct_batch* batch, int32_t what, const fitoct_summary_config* cfg,
+                            double* out);
+/* The curves of picked draws without a download (plotExpGP.R's nMC = 100 spaghetti draws):
+ * pick[j] is a flat post-warmup draw index chain * n + iteration in [0, S),
+ * n = iters_saved - first_iter.  Per group, in the groups' order: dL, m, resid [n_pick][N_g],
+ * br [n_pick] = mean(resid^2), each NULL if not wanted.  cfg: first_iter and device are read.
+ * FITOCT_E_ARG for n_pick < 0 or an index outside [0, S); otherwise refused as the bands. */
+int32_t fitoct_curves_pick_device(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                                  int32_t iters_saved, const void* d_draws,
+                                  const fitoct_summary_config* cfg, void* stream, int32_t n_pick,
+                                  const int64_t* pick, double* dL, double* m, double* resid,
+                                  double* br);
+int32_t fitoct_plan_curves_pick(fitoct_plan* plan, const fitoct_summary_config* cfg,
+                                int32_t n_pick, const int64_t* pick, double* dL, double* m,
+                                double* resid, double* br);
+int32_t fitoct_batch_curves_pick(fitoct_batch* batch, int32_t group,
+                                 const fitoct_summary_config* cfg, int32_t n_pick,
+                                 const int64_t* pick, double* dL, double* m, double* resid,
+                                 double* br);
+/* theta [n_pick][3] and yGP [n_pick][Nn] (OUTPUT-layout values; yGP may be NULL, and is not
+ * written for FITOCT_MODEL_MONOEXP) of the same picked draws of the last run */
+int32_t fitoct_plan_curves_pick_params(fitoct_plan* plan, const fitoct_summary_config* cfg,
+                                       int32_t n_pick, const int64_t* pick, double* theta,
+                                       double* ygp);
+int32_t fitoct_batch_curves_pick_params(fitoct_batch* batch, int32_t group,
+                                        const fitoct_summary_config* cfg, int32_t n_pick,
+                                        const int64_t* pick, double* theta, double* ygp);
 
 #ifdef __cplusplus
 }
