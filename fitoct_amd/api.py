@@ -210,29 +210,55 @@ def _problem_array(prob):
     return probs, arr   # probs keeps the numpy buffers behind arr alive
 
 
+def _post_warmup(cfg: SamplerConfig, first_iter):
+    """The saved iterations a handle's table skips: the caller's, or the saved warmup."""
+    if first_iter is None:
+        return cfg.warmup if cfg.save_warmup else 0
+    return first_iter
+
+
+def _n_out(problem_c) -> int:
+    """Rows of one group's summary or monitor table: 7 sampler columns, then the parameters."""
+    return 7 + lib().fitoct_output_n_params(C.byref(problem_c))
+
+
+def _host_draws(draws, ps) -> np.ndarray:
+    """Host draws of the problems ``ps`` as ``[groups, chains, iters_saved, n_cols]``."""
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    if draws.ndim == 3:
+        draws = draws[None]
+    if draws.ndim != 4 or draws.shape[0] != len(ps):
+        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
+    if draws.shape[3] != ps[0].D + 8:
+        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    return draws
+
+
+def _select_columns(prob: ExpGPProblem, pars):
+    """(output column names, indices of the rows ``pars`` selects): names or base names
+    (``"theta"`` -> ``theta.1`` ...) as in rstan, every row for None."""
+    from .stanfit import _base, output_columns
+    names = output_columns(prob)
+    if pars is None:
+        return names, list(range(len(names)))
+    sel = []
+    for p in ([pars] if isinstance(pars, str) else pars):
+        hit = [i for i, c in enumerate(names) if c == p or _base(c) == p]
+        if not hit:
+            raise KeyError(f"no parameter {p!r} in the fit")
+        sel += hit
+    return names, sel
+
+
 def summary_rows(table: np.ndarray, prob: ExpGPProblem, probs=DEFAULT_PROBS, pars=None) -> dict:
     """One group's summary table ``[P, 5 + len(probs)]`` (``fitoct_summary_*``) as the dict
     :meth:`fitoct_amd.stanfit.StanFit.summary` returns: ``{name: {"mean", "se_mean", "sd",
     "2.5%", ..., "n_eff", "Rhat"}}``, all-NaN rows omitted, ``pars`` selecting names or base
     names (``"theta"`` -> ``theta.1`` ...) as in rstan."""
-    from .stanfit import _base, output_columns
-    names = output_columns(prob)
-    if pars is None:
-        sel = list(range(len(names)))
-    else:
-        sel = []
-        for p in ([pars] if isinstance(pars, str) else pars):
-            hit = [i for i, c in enumerate(names) if c == p or _base(c) == p]
-            if not hit:
-                raise KeyError(f"no parameter {p!r} in the fit")
-            sel += hit
+    names, sel = _select_columns(prob, pars)
     keys = ["mean", "se_mean", "sd"] + [f"{100 * p:g}%" for p in probs] + ["n_eff", "Rhat"]
-    rows = {}
-    for i in sel:
-        if np.all(np.isnan(table[i])):
-            continue
-        rows[names[i]] = {k: float(v) for k, v in zip(keys, table[i])}
-    return rows
+    return {names[i]: {k: float(v) for k, v in zip(keys, table[i])}
+            for i in sel if not np.all(np.isnan(table[i]))}
 
 
 def summary_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter: int = 0,
@@ -244,9 +270,7 @@ def summary_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter
     group.  Returns ``[groups, P, 5 + len(probs)]`` (rows: :func:`summary_rows`)."""
     ps, arr = _problem_array(prob)
     c = _summary_config(first_iter, probs, max_staging_bytes, device)
-    width = 5 + c.n_probs
-    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
-    out = np.empty((len(ps), max(n_out, 0), width))
+    out = np.empty((len(ps), _n_out(arr[0]), 5 + c.n_probs))
     check(lib().fitoct_summary_device(arr, len(ps), int(chains), int(iters_saved),
                                       C.c_void_p(d_draws or None), C.byref(c),
                                       C.c_void_p(stream or None), dptr(out)))
@@ -257,16 +281,9 @@ def summary_host(draws: np.ndarray, prob, first_iter: int = 0, probs=DEFAULT_PRO
     """The same table computed on the host (``fitoct_summary_host``) from raw draws
     ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
     ps, arr = _problem_array(prob)
-    draws = np.ascontiguousarray(draws, dtype=np.float64)
-    if draws.ndim == 3:
-        draws = draws[None]
-    if draws.ndim != 4 or draws.shape[0] != len(ps):
-        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
-    if draws.shape[3] != ps[0].D + 8:
-        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    draws = _host_draws(draws, ps)
     c = _summary_config(first_iter, probs)
-    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
-    out = np.empty((len(ps), max(n_out, 0), 5 + c.n_probs))
+    out = np.empty((len(ps), _n_out(arr[0]), 5 + c.n_probs))
     check(lib().fitoct_summary_host(arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws),
                                     C.byref(c), dptr(out)))
     return out
@@ -337,13 +354,7 @@ def curves_host(draws: np.ndarray, prob, first_iter: int = 0, probs=DEFAULT_PROB
     """The same table computed on the host (``fitoct_curves_host``) from raw draws
     ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
     ps, arr = _problem_array(prob)
-    draws = np.ascontiguousarray(draws, dtype=np.float64)
-    if draws.ndim == 3:
-        draws = draws[None]
-    if draws.ndim != 4 or draws.shape[0] != len(ps):
-        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
-    if draws.shape[3] != ps[0].D + 8:
-        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    draws = _host_draws(draws, ps)
     c = _summary_config(first_iter, probs)
     bits, out = _curves_table(ps, what, c)
     check(lib().fitoct_curves_host(arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws), bits,
@@ -379,17 +390,7 @@ def monitor_rows(table: np.ndarray, prob: ExpGPProblem, pars=None) -> dict:
     """One group's rank-diagnostics table ``[P, 5]`` (``fitoct_monitor_*``) as ``{name: {"Rhat",
     "Rhat_bulk", "Rhat_fold", "Bulk_ESS", "Tail_ESS"}}`` (``Rhat`` the rank-normalised R-hat:
     the larger of bulk and folded), all-NaN rows omitted, ``pars`` as in :func:`summary_rows`."""
-    from .stanfit import _base, output_columns
-    names = output_columns(prob)
-    if pars is None:
-        sel = list(range(len(names)))
-    else:
-        sel = []
-        for p in ([pars] if isinstance(pars, str) else pars):
-            hit = [i for i, c in enumerate(names) if c == p or _base(c) == p]
-            if not hit:
-                raise KeyError(f"no parameter {p!r} in the fit")
-            sel += hit
+    names, sel = _select_columns(prob, pars)
     return {names[i]: {k: float(v) for k, v in zip(MONITOR_KEYS, table[i])}
             for i in sel if not np.all(np.isnan(table[i]))}
 
@@ -402,8 +403,7 @@ def monitor_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter
     ``[groups, P, 5]`` (rows: :func:`monitor_rows`)."""
     ps, arr = _problem_array(prob)
     c = _summary_config(first_iter, (), max_staging_bytes, device)
-    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
-    out = np.empty((len(ps), max(n_out, 0), 5))
+    out = np.empty((len(ps), _n_out(arr[0]), 5))
     check(lib().fitoct_monitor_device(arr, len(ps), int(chains), int(iters_saved),
                                       C.c_void_p(d_draws or None), C.byref(c),
                                       C.c_void_p(stream or None), dptr(out)))
@@ -414,16 +414,9 @@ def monitor_host(draws: np.ndarray, prob, first_iter: int = 0) -> np.ndarray:
     """The same table computed on the host (``fitoct_monitor_host``) from raw draws
     ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
     ps, arr = _problem_array(prob)
-    draws = np.ascontiguousarray(draws, dtype=np.float64)
-    if draws.ndim == 3:
-        draws = draws[None]
-    if draws.ndim != 4 or draws.shape[0] != len(ps):
-        raise ValueError("draws must be [groups, chains, iters_saved, n_cols], one problem per group")
-    if draws.shape[3] != ps[0].D + 8:
-        raise ValueError(f"draws have {draws.shape[3]} columns, the model has {ps[0].D + 8}")
+    draws = _host_draws(draws, ps)
     c = _summary_config(first_iter, ())
-    n_out = 7 + lib().fitoct_output_n_params(C.byref(arr[0]))
-    out = np.empty((len(ps), max(n_out, 0), 5))
+    out = np.empty((len(ps), _n_out(arr[0]), 5))
     check(lib().fitoct_monitor_host(arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws),
                                     C.byref(c), dptr(out)))
     return out
@@ -447,12 +440,60 @@ class SampleOutput:
     paired_transitions: int = 0      # ... whose forward end grew in a partner tile (no effect)
 
 
-class Plan:
+class _LastRun:
+    """The posterior tables of a handle's last run, computed on the device from the draws where
+    they lie: the bodies :class:`Plan` and :class:`Batch` share.  The handle gives ``_h``,
+    ``cfg``, ``info``, its problems ``_probs`` with the first as a C struct ``_p0``, and the
+    prefix of its entry points ``_entries`` ("fitoct_plan_" / "fitoct_batch_").  Every body
+    returns one dict per problem, or with ``problem`` that problem's dict."""
+
+    def _entry(self, name):
+        return getattr(lib(), self._entries + name)
+
+    def _each(self, problem, rows):
+        if problem is not None:
+            return rows(problem)
+        return [rows(p) for p in range(len(self._probs))]
+
+    def _summary(self, problem, pars, probs, first_iter, max_staging_bytes):
+        c = _summary_config(_post_warmup(self.cfg, first_iter), probs, max_staging_bytes)
+        out = np.empty((len(self._probs), _n_out(self._p0), 5 + c.n_probs))
+        check(self._entry("summary")(self._h, C.byref(c), dptr(out)))
+        return self._each(problem, lambda p: summary_rows(out[p], self._probs[p], probs, pars))
+
+    def _monitor(self, problem, pars, first_iter, max_staging_bytes):
+        c = _summary_config(_post_warmup(self.cfg, first_iter), (), max_staging_bytes)
+        out = np.empty((len(self._probs), _n_out(self._p0), 5))
+        check(self._entry("monitor")(self._h, C.byref(c), dptr(out)))
+        return self._each(problem, lambda p: monitor_rows(out[p], self._probs[p], pars))
+
+    def _curves(self, problem, what, probs, first_iter, max_staging_bytes):
+        c = _summary_config(_post_warmup(self.cfg, first_iter), probs, max_staging_bytes)
+        bits, out = _curves_table(self._probs, what, c)
+        check(self._entry("curves")(self._h, bits, C.byref(c), dptr(out)))
+        blocks = curves_blocks(out, self._probs, bits, probs)
+        return self._each(problem, lambda p: curves_rows(blocks[p], self._probs[p], bits, probs))
+
+    def _curves_pick(self, problem, chains, draws, n, seed, first_iter, *lead):
+        """``lead``: what the pick entries take between the handle and the config."""
+        first_iter = _post_warmup(self.cfg, first_iter)
+        idx = _pick_indices(draws, n, seed, chains * (self.info["iters_saved"] - first_iter))
+        c = _summary_config(first_iter, ())
+        pick, params = self._entry("curves_pick"), self._entry("curves_pick_params")
+        return _pick(self._probs[problem], idx,
+                     lambda k, ip, *o: pick(self._h, *lead, C.byref(c), k, ip, *o),
+                     lambda k, ip, *o: params(self._h, *lead, C.byref(c), k, ip, *o))
+
+
+class Plan(_LastRun):
     """A planned sampler run: inputs staged in HBM once, run many times."""
+
+    _entries = "fitoct_plan_"
 
     def __init__(self, prob: ExpGPProblem, cfg: SamplerConfig):
         self.prob, self.cfg = prob, cfg
         self._p = prob.to_c()
+        self._probs, self._p0 = [prob], self._p
         self._c = cfg.to_c()
         h = C.c_void_p()
         check(lib().fitoct_plan_create(C.byref(self._p), C.byref(self._c), C.byref(h)))
@@ -556,24 +597,12 @@ class Plan:
         the draws where they lie (the plan's buffer or the ``d_draws`` of the run; nothing is
         downloaded but the table): the dict of :meth:`fitoct_amd.stanfit.StanFit.summary`.
         ``first_iter`` (saved iterations to skip) defaults to the saved warmup."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        c = _summary_config(first_iter, probs, max_staging_bytes)
-        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._p))
-        out = np.empty((n_out, 5 + c.n_probs))
-        check(lib().fitoct_plan_summary(self._h, C.byref(c), dptr(out)))
-        return summary_rows(out, self.prob, probs, pars)
+        return self._summary(0, pars, probs, first_iter, max_staging_bytes)
 
     def monitor(self, pars=None, first_iter=None, max_staging_bytes: int = 0) -> dict:
         """``rstan::monitor``'s rank diagnostics of the last run, computed on the device from
         the draws where they lie (as :meth:`summary`): the dict of :func:`monitor_rows`."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        c = _summary_config(first_iter, (), max_staging_bytes)
-        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._p))
-        out = np.empty((n_out, 5))
-        check(lib().fitoct_plan_monitor(self._h, C.byref(c), dptr(out)))
-        return monitor_rows(out, self.prob, pars)
+        return self._monitor(0, pars, first_iter, max_staging_bytes)
 
     def curves(self, what=CURVE_NAMES, probs=DEFAULT_PROBS, first_iter=None,
                max_staging_bytes: int = 0) -> dict:
@@ -581,26 +610,13 @@ class Plan:
         the device from the draws where they lie: ``{"dL": {"mean": [N], "sd": [N], "2.5%":
         [N], ...}, "m": ..., "resid": ..., "x": x}`` for the quantities named in ``what``.
         ``first_iter`` defaults to the saved warmup."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        c = _summary_config(first_iter, probs, max_staging_bytes)
-        bits, out = _curves_table([self.prob], what, c)
-        check(lib().fitoct_plan_curves(self._h, bits, C.byref(c), dptr(out)))
-        return curves_rows(curves_blocks(out, [self.prob], bits, probs)[0], self.prob, bits, probs)
+        return self._curves(0, what, probs, first_iter, max_staging_bytes)
 
     def curves_pick(self, draws=None, n=100, seed=None, first_iter=None) -> dict:
         """:func:`fitoct_amd.genquant.generated_quantities` without the download: dict(index,
         theta, yGP, dL, m, resid, br) of ``n`` post-warmup draws chosen at random (``seed``) or
         of the flat indices ``draws`` (chain * n_post + iteration), evaluated on the device."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        S = self.info["chains"] * (self.info["iters_saved"] - first_iter)
-        idx = _pick_indices(draws, n, seed, S)
-        c = _summary_config(first_iter, ())
-        L, h = lib(), self._h
-        return _pick(self.prob, idx,
-                     lambda k, ip, *o: L.fitoct_plan_curves_pick(h, C.byref(c), k, ip, *o),
-                     lambda k, ip, *o: L.fitoct_plan_curves_pick_params(h, C.byref(c), k, ip, *o))
+        return self._curves_pick(0, self.info["chains"], draws, n, seed, first_iter)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -620,11 +636,13 @@ class Plan:
         self.close()
 
 
-class Batch:
+class Batch(_LastRun):
     """Many problems (FitOCT.R's per-file fits, FitOCT.R:70-124) sampled by one
     launch (``fitoct_batch_*``).  Problem ``p``'s chains are global chains
     ``cfg.chain_offset + p*cfg.chains + c``, so its draws equal a :class:`Plan`
     of that problem with ``chain_offset = cfg.chain_offset + p*cfg.chains``."""
+
+    _entries = "fitoct_batch_"
 
     def __init__(self, probs, cfg: SamplerConfig):
         self.probs, self.cfg = list(probs), cfg
@@ -634,6 +652,7 @@ class Batch:
         for i, p in enumerate(self.probs):
             arr[i] = p.to_c()
         self._arr = arr    # the problems' numpy buffers stay referenced by self.probs
+        self._probs, self._p0 = self.probs, arr[0]
         self._c = cfg.to_c()
         h = C.c_void_p()
         check(lib().fitoct_batch_create(arr, len(self.probs), C.byref(self._c), C.byref(h)))
@@ -675,54 +694,23 @@ class Batch:
                 max_staging_bytes: int = 0):
         """Device summary of the last run (:meth:`Plan.summary`) of every file in one call: a
         list with one dict per problem, or problem ``problem``'s dict."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        c = _summary_config(first_iter, probs, max_staging_bytes)
-        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._arr[0]))
-        out = np.empty((len(self.probs), n_out, 5 + c.n_probs))
-        check(lib().fitoct_batch_summary(self._h, C.byref(c), dptr(out)))
-        if problem is not None:
-            return summary_rows(out[problem], self.probs[problem], probs, pars)
-        return [summary_rows(out[p], self.probs[p], probs, pars) for p in range(len(self.probs))]
+        return self._summary(problem, pars, probs, first_iter, max_staging_bytes)
 
     def monitor(self, problem=None, pars=None, first_iter=None, max_staging_bytes: int = 0):
         """Device rank diagnostics of the last run (:meth:`Plan.monitor`) of every file in one
         call: a list with one dict per problem, or problem ``problem``'s dict."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        c = _summary_config(first_iter, (), max_staging_bytes)
-        n_out = 7 + lib().fitoct_output_n_params(C.byref(self._arr[0]))
-        out = np.empty((len(self.probs), n_out, 5))
-        check(lib().fitoct_batch_monitor(self._h, C.byref(c), dptr(out)))
-        if problem is not None:
-            return monitor_rows(out[problem], self.probs[problem], pars)
-        return [monitor_rows(out[p], self.probs[p], pars) for p in range(len(self.probs))]
+        return self._monitor(problem, pars, first_iter, max_staging_bytes)
 
     def curves(self, problem=None, what=CURVE_NAMES, probs=DEFAULT_PROBS, first_iter=None,
                max_staging_bytes: int = 0):
         """Posterior bands of the last run (:meth:`Plan.curves`) of every file in one call: a
         list with one dict per problem, or problem ``problem``'s dict."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        c = _summary_config(first_iter, probs, max_staging_bytes)
-        bits, out = _curves_table(self.probs, what, c)
-        check(lib().fitoct_batch_curves(self._h, bits, C.byref(c), dptr(out)))
-        blocks = curves_blocks(out, self.probs, bits, probs)
-        if problem is not None:
-            return curves_rows(blocks[problem], self.probs[problem], bits, probs)
-        return [curves_rows(b, p, bits, probs) for b, p in zip(blocks, self.probs)]
+        return self._curves(problem, what, probs, first_iter, max_staging_bytes)
 
     def curves_pick(self, problem: int, draws=None, n=100, seed=None, first_iter=None) -> dict:
         """:meth:`Plan.curves_pick` for problem ``problem`` of the last run."""
-        if first_iter is None:
-            first_iter = self.cfg.warmup if self.cfg.save_warmup else 0
-        S = self.cfg.chains * (self.info["iters_saved"] - first_iter)
-        idx = _pick_indices(draws, n, seed, S)
-        c = _summary_config(first_iter, ())
-        L, h, g = lib(), self._h, int(problem)
-        return _pick(self.probs[g], idx,
-                     lambda k, ip, *o: L.fitoct_batch_curves_pick(h, g, C.byref(c), k, ip, *o),
-                     lambda k, ip, *o: L.fitoct_batch_curves_pick_params(h, g, C.byref(c), k, ip, *o))
+        g = int(problem)
+        return self._curves_pick(g, self.cfg.chains, draws, n, seed, first_iter, g)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -44,7 +44,9 @@ SOURCES = [
     ("nuts_lasso", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=1"]),
     ("nuts_horseshoe", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=2"]),
     ("nuts_monoexp", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=3"]),
-    # the posterior summary's kernels and entry points (no family parameter)
+    # what the three posterior tables below share: its kernels, compiled once (no family parameter)
+    ("posterior_common", "posterior_common.hip", "hipcc", _KERNEL),
+    # the posterior summary's entry points
     ("summary_device", "summary_device.hip", "hipcc", _KERNEL),
     # the rank diagnostics' kernels (the device sort) and entry points
     ("monitor_device", "monitor_device.hip", "hipcc", _KERNEL),
@@ -59,8 +61,8 @@ SOURCES = [
     ("stamps_report", "stamps_report.cpp", "g++", ["-O2", "-std=c++17"]),
 ]
 # objects whose kernels' resource remarks are kept beside them (<object>.resources.txt)
-RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["summary_device", "monitor_device",
-                                                                         "curves_device"]
+RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["posterior_common", "summary_device",
+                                                                         "monitor_device", "curves_device"]
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")

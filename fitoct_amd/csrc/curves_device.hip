@@ -6,32 +6,19 @@
 // one curve_bin of summary_shared.h.
 //
 // Device route:
-//   params_kernel  once per call: raw rows (read coalesced through LDS, as stage_kernel does)
+//   params_kernel  once per call: raw rows (read coalesced through LDS: load_row_tile)
 //                  -> Pm[group][S][3 + Nn], theta and yGP of every pooled draw in the OUTPUT
 //                  layout's values, chain-major; a NaN among them flags its group;
 //   curve_kernel   per pass: a workgroup takes 256 consecutive pooled draws of one group, each
 //                  lane its draw's theta and yGP in registers, and loops over up to CURVE_CHUNK
 //                  (quantity, bin) pairs whose basis rows, -c x, y and uy it staged in LDS
 //                  (every lane reads the same word: a broadcast); lane s stores X[pair][s];
-//   moments_kernel, qhist_kernel / qselect_kernel (summary_kernels.h) reduce X[pair][chain][n]
-//                  exactly as the summary does; the host forms the rows.
+//   queue_moments, queue_select (the shared layer, posterior_common.hip) reduce
+//                  X[pair][chain][n] exactly as the summary does; pair_row forms the rows.
 //   curve_pick_kernel  one workgroup per (group, picked draw): the draw's curves over the
 //                  bins and br = mean(resid^2), reduced in a fixed order.
 // No floating-point atomics: the table is the same bytes from call to call and for any pass size.
-#include <hip/hip_runtime.h>
-
-#include <math.h>
-#include <stdint.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "fitoct.h"
-#include "host_internal.h"
-#include "plan_internal.h"
-#include "summary_kernels.h"
-#include "summary_shared.h"
+#include "posterior_common.h"
 
 namespace fitoct {
 namespace {
@@ -130,20 +117,10 @@ struct Seg {
 __global__ __launch_bounds__(STAGE_THREADS) void params_kernel(KShape k, int npar,
                                                                const double* draws, double* Pm,
                                                                int* group_nan) {
-  extern __shared__ double tile[];   // [STAGE_ROWS][Wp], Wp odd: rows land on different banks
+  extern __shared__ double tile[];   // [STAGE_ROWS][Wp]
   const int Wp = k.W | 1;
-  const int rblocks = (k.n + STAGE_ROWS - 1) / STAGE_ROWS;
-  int64_t b = blockIdx.x;
-  const int rb = (int)(b % rblocks);
-  b /= rblocks;
-  const int c = (int)(b % k.C), g = (int)(b / k.C);
-  const int i0 = rb * STAGE_ROWS, rows = min(STAGE_ROWS, k.n - i0);
-  const double* src = draws + (((size_t)g * k.C + c) * k.I + k.first + i0) * k.W;
-  for (int t = threadIdx.x; t < rows * k.W; t += STAGE_THREADS) {
-    const int r = t / k.W;
-    tile[r * Wp + (t - r * k.W)] = src[t];
-  }
-  __syncthreads();
+  const RowBlock rb = load_row_tile(k, draws, tile);
+  const int g = rb.g, c = rb.c, i0 = rb.i0, rows = rb.rows;
   // pooled draw s = chain * n + iteration; a row's npar values are contiguous
   double* dst = Pm + (((size_t)g * k.C + c) * k.n + i0) * npar;
   int bad = 0;
@@ -278,25 +255,17 @@ struct CurveDev {
   }
 };
 
-KShape kshape(const Shape& s) {
-  return KShape{s.G, s.C, s.I, s.W, s.first, s.n, s.h, s.m, 0, 0, s.model};
-}
-
 int curves_device(const fitoct_problem* probs, const Shape& s, const CShape& c, const void* d_draws,
                   const fitoct_summary_config* cfg, hipStream_t st, double* out) {
   DeviceKeep keep;
   HIP_TRY(hipSetDevice(cfg->device));
   const int width = 2 + s.np, T = 2 * s.np;
-  // pairs per pass: columns_per_pass's arithmetic on pairs of S doubles
-  const int64_t cap = cfg->max_staging_bytes > 0 ? cfg->max_staging_bytes : DEFAULT_STAGING_BYTES;
-  const int64_t ppp = std::max<int64_t>(
-      1, std::min<int64_t>(std::min<int64_t>(c.pairs, CURVE_MAX_PAIRS),
-                           cap / (s.S * (int64_t)sizeof(double))));
+  const int64_t ppp = items_per_pass(cfg, std::min<int64_t>(c.pairs, CURVE_MAX_PAIRS),
+                                     s.S * (int64_t)sizeof(double));   // pairs of S doubles
   const int tiles = (int)((s.S + CURVE_THREADS - 1) / CURVE_THREADS);
-  const int rblocks = (s.n + STAGE_ROWS - 1) / STAGE_ROWS;
   const int nblk = qhist_blocks(s.S);
   const int64_t limit = (int64_t)1 << 31;
-  if ((int64_t)rblocks * s.C * s.G >= limit || ppp * s.m >= limit || ppp * nblk >= limit ||
+  if (row_grid(s) >= limit || ppp * s.m >= limit || ppp * nblk >= limit ||
       (ppp + s.G) * tiles >= limit || s.S >= limit)
     return fail(FITOCT_E_ARG, "curves: shape too large for one launch (lower max_staging_bytes)");
 
@@ -335,15 +304,12 @@ int curves_device(const fitoct_problem* probs, const Shape& s, const CShape& c, 
   std::vector<int> h_gnan(s.G);
   HIP_TRY(hipMemsetAsync(gnan.p, 0, (size_t)s.G * sizeof(int), st));
   HIP_TRY(hipMemcpyAsync(dsegs.p, segs.data(), segs.size() * sizeof(Seg), hipMemcpyHostToDevice, st));
-  params_kernel<<<dim3((unsigned)((int64_t)rblocks * s.C * s.G)), dim3(STAGE_THREADS),
-                  sizeof(double) * STAGE_ROWS * (s.W | 1), st>>>(k, c.npar, (const double*)d_draws,
-                                                                 Pm.as<double>(), gnan.as<int>());
+  params_kernel<<<dim3((unsigned)row_grid(s)), dim3(STAGE_THREADS), row_tile_bytes(s.W), st>>>(
+      k, c.npar, (const double*)d_draws, Pm.as<double>(), gnan.as<int>());
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h_gnan.data(), gnan.p, (size_t)s.G * sizeof(int), hipMemcpyDeviceToHost, st));
 
-  std::vector<QIndex> qidx(s.np);
-  for (int i = 0; i < s.np; ++i) qidx[i] = quantile_index(s.S, cfg->probs[i]);
-  const SelectRanks ranks(qidx, ppp);
+  const SelectRanks ranks(s, cfg, ppp);
   std::vector<double> h_mom;
   std::vector<int> h_flags;
   std::vector<unsigned long long> h_keys;
@@ -362,17 +328,8 @@ int curves_device(const fitoct_problem* probs, const Shape& s, const CShape& c, 
     int g = 0;
     for (int64_t p = 0; p < pairs; ++p) {
       while (c.bin_off[g + 1] * c.nq <= p0 + p) ++g;
-      double* row = out + (size_t)(p0 + p) * width;
-      int fl = h_gnan[g] ? 1 : 0;
-      for (int j = 0; j < s.m; ++j) fl |= h_flags[(size_t)p * s.m + j] & 1;
-      if (fl) {
-        for (int i = 0; i < width; ++i) row[i] = NAN;
-        continue;
-      }
-      pooled_mean_sd(h_mom.data() + (size_t)p * s.m * 4, s.n, s.h, s.m, s.S, row[0], row[1]);
-      for (int i = 0; i < s.np; ++i)
-        row[2 + i] = quantile_lerp(key_value(h_keys[p * QT_MAX + 2 * i]),
-                                   key_value(h_keys[p * QT_MAX + 2 * i + 1]), qidx[i].frac);
+      pair_row(s, p, h_mom, h_flags, h_keys, ranks, h_gnan[g] != 0, out + (size_t)(p0 + p) * width,
+               width, 1);
     }
   }
   return FITOCT_OK;
@@ -457,68 +414,13 @@ int curves_pick_checked(const fitoct_problem* probs, int n_groups, int chains, i
                      br, theta, ygp);
 }
 
-// ---- the last run of a plan or a batch ------------------------------------------------------
-// a plan's problem with the plan's own copies of x, y, uy and the basis behind it
-fitoct_problem with_data(const fitoct_plan* pl) {
-  fitoct_problem p = pl->prob;
-  if (pl->h_xyu.size() == 3 * (size_t)p.N) {
-    p.x = pl->h_xyu.data();
-    p.y = p.x + p.N;
-    p.uy = p.y + p.N;
-  }
-  p.B = pl->h_B.empty() ? nullptr : pl->h_B.data();
-  return p;
-}
-
-// where the last run's draws lie: the refusals of fitoct_plan_summary / fitoct_batch_summary
-struct Where {
-  std::vector<fitoct_problem> probs;
-  int chains = 0, iters_saved = 0, device = 0;
-  const char* draws = nullptr;
-  size_t group_bytes = 0;
-};
-int plan_where(fitoct_plan* pl, Where& w) {
-  if (pl->launched) return fail(FITOCT_E_ARG, "plan is running: call fitoct_plan_wait first");
-  if (!pl->ran) return fail(FITOCT_E_ARG, "plan has not run");
-  const bool group = !pl->shards.empty();
-  if (group && !pl->gather_dst)
-    return fail(FITOCT_E_ARG, "the device-list run left its shards in per-device buffers: pass "
-                              "a d_draws to the run, the curves need the draws in one buffer");
-  w.probs.push_back(with_data(pl));
-  w.chains = pl->kp.chains;
-  w.iters_saved = pl->kp.iters_saved;
-  w.device = group ? pl->gather_dev : pl->cfg.device;
-  w.draws = (const char*)(group ? pl->gather_dst : (void*)pl->last_draws);
-  return FITOCT_OK;
-}
-int batch_where(fitoct_batch* b, Where& w) {
-  if (!b->ran) return fail(FITOCT_E_ARG, "batch has not run");
-  const bool group = !b->subs.empty();
-  if (group && !b->gather_dst)
-    return fail(FITOCT_E_ARG, "the device-list run left its files in per-device buffers: pass "
-                              "a d_draws to the run, the curves need the draws in one buffer");
-  if (group) {
-    for (const fitoct_batch* sb : b->subs)
-      for (const fitoct_plan* pl : sb->plans) w.probs.push_back(with_data(pl));
-  } else {
-    for (const fitoct_plan* pl : b->plans) w.probs.push_back(with_data(pl));
-  }
-  const fitoct_plan* p0 = group ? b->subs[0]->plans[0] : b->plans[0];
-  w.chains = b->cfg.chains;
-  w.iters_saved = p0->kp.iters_saved;
-  w.device = group ? b->gather_dev : b->cfg.device;
-  w.draws = (const char*)(group ? b->gather_dst : (void*)p0->last_draws);
-  w.group_bytes = sizeof(double) * (size_t)w.chains * w.iters_saved *
-                  (model_dim(p0->prob.prior_type, p0->prob.Nn) + 8);
-  return FITOCT_OK;
-}
-
+// ---- the last run of a plan or a batch (plan_where / batch_where: the refusals) --------------
 int batch_pick(fitoct_batch* b, int group, const fitoct_summary_config* cfg, int n_pick,
                const int64_t* pick, double* dL, double* m, double* resid, double* br,
                double* theta, double* ygp) {
   if (!b || !cfg) return fail(FITOCT_E_ARG, "curves pick: NULL argument");
   Where w;
-  FITOCT_TRY(batch_where(b, w));
+  FITOCT_TRY(batch_where(b, "the curves need", w));
   if (group < 0 || group >= (int)w.probs.size())
     return fail(FITOCT_E_ARG, "curves pick: group out of range");
   fitoct_summary_config c = *cfg;
@@ -532,7 +434,7 @@ int plan_pick(fitoct_plan* pl, const fitoct_summary_config* cfg, int n_pick, con
               double* dL, double* m, double* resid, double* br, double* theta, double* ygp) {
   if (!pl || !cfg) return fail(FITOCT_E_ARG, "curves pick: NULL argument");
   Where w;
-  FITOCT_TRY(plan_where(pl, w));
+  FITOCT_TRY(plan_where(pl, "the curves need", w));
   fitoct_summary_config c = *cfg;
   c.device = w.device;
   return curves_pick_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, &c, nullptr,
@@ -577,7 +479,7 @@ int32_t fitoct_plan_curves(fitoct_plan* pl, int32_t what, const fitoct_summary_c
   return guarded(__func__, [&]() -> int32_t {
     if (!pl || !cfg || !out) return fail(FITOCT_E_ARG, "curves: NULL argument");
     Where w;
-    FITOCT_TRY(plan_where(pl, w));
+    FITOCT_TRY(plan_where(pl, "the curves need", w));
     fitoct_summary_config c = *cfg;
     c.device = w.device;
     return curves_device_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, what, &c,
@@ -590,7 +492,7 @@ int32_t fitoct_batch_curves(fitoct_batch* b, int32_t what, const fitoct_summary_
   return guarded(__func__, [&]() -> int32_t {
     if (!b || !cfg || !out) return fail(FITOCT_E_ARG, "curves: NULL argument");
     Where w;
-    FITOCT_TRY(batch_where(b, w));
+    FITOCT_TRY(batch_where(b, "the curves need", w));
     fitoct_summary_config c = *cfg;
     c.device = w.device;
     return curves_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains, w.iters_saved,

@@ -4,8 +4,8 @@
 // same computation on the host (fitoct_monitor_host, on top of host_model.cpp's monitor_column)
 // that the device route is tested against.
 //
-// Device route, per pass over a chunk of output columns (stage_kernel, moments_kernel,
-// acov_kernel and Geyer's rounds: summary_kernels.h, shared with the summary):
+// Device route, per pass over a chunk of output columns (queue_stage, queue_moments and
+// ess_rounds: the shared layer, posterior_common.hip, which holds their kernels):
 //   stage_kernel      raw rows -> X[pair][chain][n], the output-layout transform applied;
 //   keys_kernel       the S = 2 chains h split draws of a pair, pooled in split-chain order, as
 //                     order-preserving 64-bit keys (of x, or of |x - median|);
@@ -27,20 +27,7 @@
 //   on the host for the first three: the four series lie in one buffer, one launch serves all.
 // No floating-point atomics anywhere, and no result depends on the order in which workgroups
 // run: the results are the same bit for bit from call to call and for any max_staging_bytes.
-#include <hip/hip_runtime.h>
-
-#include <math.h>
-#include <stdint.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "fitoct.h"
-#include "host_internal.h"
-#include "plan_internal.h"
-#include "summary_kernels.h"
-#include "summary_shared.h"
+#include "posterior_common.h"
 
 namespace fitoct {
 namespace {
@@ -276,14 +263,13 @@ int monitor_device(const Shape& s, const void* d_draws, const fitoct_summary_con
   HIP_TRY(hipSetDevice(cfg->device));
   const int64_t S = (int64_t)s.m * s.h;   // pooled split draws of one column
   const int64_t col_bytes = (int64_t)s.G * s.S * (int64_t)sizeof(double);
-  const int ncc_max = columns_per_pass(s, cfg, FITOCT_MONITOR_STAGING_BUFFERS * col_bytes);
+  const int ncc_max = (int)items_per_pass(cfg, s.P, FITOCT_MONITOR_STAGING_BUFFERS * col_bytes);
   const int64_t pairs_max = (int64_t)s.G * ncc_max;
-  const int rblocks = (s.n + STAGE_ROWS - 1) / STAGE_ROWS;
   const int64_t nblk = (S + ELEM_THREADS - 1) / ELEM_THREADS;
   const int64_t ntile = (S + SORT_TILE - 1) / SORT_TILE;
   const int64_t limit = (int64_t)1 << 31;
   // (the radix offsets and the average rank's lower + upper are 32- and 64-bit: S < 2^31)
-  if (S >= limit || (int64_t)rblocks * s.C * s.G >= limit || N_SERIES * pairs_max * s.m >= limit ||
+  if (S >= limit || row_grid(s) >= limit || N_SERIES * pairs_max * s.m >= limit ||
       pairs_max * nblk >= limit || pairs_max * ntile * 256 >= limit)
     return fail(FITOCT_E_ARG, "monitor: shape too large for one launch (lower max_staging_bytes)");
 
@@ -310,19 +296,17 @@ int monitor_device(const Shape& s, const void* d_draws, const fitoct_summary_con
   for (int c0 = 0; c0 < s.P; c0 += ncc_max) {
     const int ncc = std::min(ncc_max, s.P - c0);
     const int64_t pairs = (int64_t)s.G * ncc;
-    const KShape k{s.G, s.C, s.I, s.W, s.first, s.n, s.h, s.m, c0, ncc, s.model};
+    const KShape k = kshape(s, c0, ncc);
     // Z[pair][split chain][h] read as whole chains of 2 h draws: the split halves are its rows
-    const KShape kz{s.G, s.C, s.I, s.W, s.first, 2 * s.h, s.h, s.m, c0, ncc, s.model};
+    KShape kz = k;
+    kz.n = 2 * s.h;
     const dim3 egrid((unsigned)(pairs * nblk)), eblock(ELEM_THREADS);
     unsigned long long* keys = KA.as<unsigned long long>();
     // this pass's series: pair p of series q is "pair" q pairs + p of the moments and Geyer's rounds
     double* Z = ZS.as<double>();
     double *I05 = Z + (size_t)pairs * S, *I95 = Z + (size_t)2 * pairs * S,
            *ZF = Z + (size_t)3 * pairs * S;
-    stage_kernel<<<dim3((unsigned)((int64_t)rblocks * s.C * s.G)), dim3(STAGE_THREADS),
-                   sizeof(double) * STAGE_ROWS * (s.W | 1), st>>>(
-        k, (const double*)d_draws, lscale.as<double>(), X.as<double>());
-    HIP_TRY(hipGetLastError());
+    FITOCT_TRY(queue_stage(k, d_draws, lscale.as<double>(), X.as<double>(), st));
 
     // x: sort, the order statistics, z(x)
     keys_kernel<<<egrid, eblock, 0, st>>>(k, X.as<double>(), par.as<double>(), 0, S, (int)nblk, keys);
@@ -381,11 +365,7 @@ int monitor_device(const Shape& s, const void* d_draws, const fitoct_summary_con
     FITOCT_TRY(ess_rounds(kz, Z, eb, st, mom, active, ess));
 
     auto psr_of = [&](int64_t p) {   // p: series and pair
-      const double* mo = mom.data() + (size_t)p * s.m * 4;
-      for (int j = 0; j < s.m; ++j) {
-        cm[j] = mo[4 * j];
-        cv[j] = mo[4 * j + 1] / (s.h - 1);
-      }
+      split_moments(mom.data() + (size_t)p * s.m * 4, s.m, s.h, cm.data(), cv.data());
       return psr_moments(cm.data(), cv.data(), s.m, s.h);
     };
     for (int64_t p = 0; p < pairs; ++p) {
@@ -442,41 +422,24 @@ int32_t fitoct_monitor_device(const fitoct_problem* probs, int32_t n_groups, int
 int32_t fitoct_plan_monitor(fitoct_plan* pl, const fitoct_summary_config* cfg, double* out) {
   return guarded(__func__, [&]() -> int32_t {
     if (!pl || !cfg || !out) return fail(FITOCT_E_ARG, "monitor: NULL argument");
-    if (pl->launched)
-      return fail(FITOCT_E_ARG, "plan is running: call fitoct_plan_wait first");
-    if (!pl->ran) return fail(FITOCT_E_ARG, "plan has not run");
-    const bool group = !pl->shards.empty();
-    if (group && !pl->gather_dst)
-      return fail(FITOCT_E_ARG, "the device-list run left its shards in per-device buffers: pass "
-                                "a d_draws to the run, the diagnostics need the draws in one buffer");
+    Where w;
+    FITOCT_TRY(plan_where(pl, "the diagnostics need", w));
     fitoct_summary_config c = *cfg;
-    c.device = group ? pl->gather_dev : pl->cfg.device;
-    return monitor_device_checked(&pl->prob, 1, pl->kp.chains, pl->kp.iters_saved,
-                                  group ? pl->gather_dst : (void*)pl->last_draws, &c, nullptr, out);
+    c.device = w.device;
+    return monitor_device_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, &c, nullptr,
+                                  out);
   });
 }
 
 int32_t fitoct_batch_monitor(fitoct_batch* b, const fitoct_summary_config* cfg, double* out) {
   return guarded(__func__, [&]() -> int32_t {
     if (!b || !cfg || !out) return fail(FITOCT_E_ARG, "monitor: NULL argument");
-    if (!b->ran) return fail(FITOCT_E_ARG, "batch has not run");
-    const bool group = !b->subs.empty();
-    if (group && !b->gather_dst)
-      return fail(FITOCT_E_ARG, "the device-list run left its files in per-device buffers: pass "
-                                "a d_draws to the run, the diagnostics need the draws in one buffer");
-    std::vector<fitoct_problem> probs;
-    if (group) {
-      for (const fitoct_batch* sb : b->subs)
-        for (const fitoct_plan* pl : sb->plans) probs.push_back(pl->prob);
-    } else {
-      for (const fitoct_plan* pl : b->plans) probs.push_back(pl->prob);
-    }
-    const fitoct_plan* p0 = group ? b->subs[0]->plans[0] : b->plans[0];
+    Where w;
+    FITOCT_TRY(batch_where(b, "the diagnostics need", w));
     fitoct_summary_config c = *cfg;
-    c.device = group ? b->gather_dev : b->cfg.device;
-    return monitor_device_checked(probs.data(), (int32_t)probs.size(), b->cfg.chains,
-                                  p0->kp.iters_saved,
-                                  group ? b->gather_dst : (void*)p0->last_draws, &c, nullptr, out);
+    c.device = w.device;
+    return monitor_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains, w.iters_saved,
+                                  w.draws, &c, nullptr, out);
   });
 }
 

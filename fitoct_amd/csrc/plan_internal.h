@@ -145,4 +145,24 @@ int batch_run_single(fitoct_batch* b, void* d_draws, void* stream);
 int check_init(int C, int D, const double* q, const double* eps, const double* minv);
 int group_batch_download(fitoct_batch* b, int problem, fitoct_result* res);
 
+// ---- where the last run's draws lie (posterior_common.hip) ----
+// What a plan's or a batch's last run left, as the arguments of a *_device entry of the
+// posterior summary, the rank diagnostics or the posterior curves.  The problems carry the
+// plans' own copies of x, y, uy and the basis (with_data): the curves read them; the summary and
+// the rank diagnostics read prior_type, Nn, prior_PD and lambda_scale only (check_args), so one
+// form serves all three.
+struct Where {
+  std::vector<fitoct_problem> probs;
+  int chains = 0, iters_saved = 0, device = 0;
+  const char* draws = nullptr;
+  size_t group_bytes = 0;   // a batch: raw bytes of one problem's draws
+};
+// a plan's problem with the plan's own copies of x, y, uy and the basis behind it
+fitoct_problem with_data(const fitoct_plan* pl);
+// The refusals: a plan in flight, a plan or batch that has not run, a device-list run that left
+// its parts in per-device buffers (`needs` names the caller in that message: "the summary needs",
+// "the diagnostics need", "the curves need").
+int plan_where(fitoct_plan* pl, const char* needs, Where& w);
+int batch_where(fitoct_batch* b, const char* needs, Where& w);
+
 }  // namespace fitoct

@@ -1,50 +1,29 @@
-// What the device routes of the posterior summary (summary_device.hip), of the rank
-// diagnostics (monitor_device.hip) and of the posterior curves (curves_device.hip) share
-// (DESIGN.md §4): the argument checks and the shape arithmetic, the staging, moments and
-// autocovariance kernels, the exact radix select of the quantiles with its set-up, the device
-// buffers, the split of the output columns into passes, and the rounds of Geyer's rule over
-// lag blocks.  Included by those translation units only; everything has internal linkage, so
-// each object carries its own copy of the kernels.
-#pragma once
-#include <hip/hip_runtime.h>
-
-#include <math.h>
-#include <stdint.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "fitoct.h"
-#include "host_internal.h"
-#include "summary_shared.h"
+// The one compiled copy of what the device routes of the posterior summary
+// (summary_device.hip), of the rank diagnostics (monitor_device.hip) and of the posterior curves
+// (curves_device.hip) share (posterior_common.h): the argument checks and the
+// shape arithmetic, where a plan's or a batch's last run left its draws, the staging, moments
+// and autocovariance kernels, the exact radix select of the quantiles with its set-up, the
+// device buffers, the rounds of Geyer's rule over lag blocks, and the head of a table row.
+//
+//   stage_kernel    raw rows (contiguous, read coalesced through LDS) -> the output-layout
+//                   transform (summary_shared.h, the copy stan_output.cpp uses) -> a
+//                   column-major post-warmup staging buffer X[group][col][chain][n];
+//   moments_kernel  one wave per (group, col, split chain): mean, then centred sum of
+//                   squares, NaN and constant flags (butterfly reductions: a fixed order);
+//   acov_kernel     per (group, col, block of 64 lags): biased autocovariance of every split
+//                   chain about its own mean, averaged over the split chains in a fixed
+//                   order.  The host applies Geyer's rule (ess_moments, shared with the host
+//                   diagnostics) block by block and asks for the next block only for the
+//                   columns that have not terminated;
+//   qhist_kernel /  exact radix select over order-preserving 64-bit keys of the pooled
+//   qselect_kernel  values: eight 8-bit passes, most significant byte first, for the up to
+//                   2 n_probs order statistics of each (group, col) at once; histograms in
+//                   LDS, merged with integer atomics; a one-wave kernel picks the digits.
+// No floating-point atomics anywhere: the results are the same bit for bit from call to call.
+#include "posterior_common.h"
 
 namespace fitoct {
-namespace {
 
-constexpr int64_t DEFAULT_STAGING_BYTES = (int64_t)256 << 20;
-constexpr int MAX_PROBS = 16;
-constexpr int LAG_BLOCK = 64;           // lags per acov_kernel workgroup: one per lane
-constexpr int STAGE_ROWS = 32;          // rows of one chain per stage_kernel workgroup
-constexpr int STAGE_THREADS = 256;
-constexpr int ACOV_WAVES = 4;
-constexpr int ACOV_TILE = 512;          // series elements per LDS tile and wave
-constexpr int QT_MAX = 2 * MAX_PROBS;   // order statistics per column: x[lo], x[hi] per probability
-constexpr int QHIST_THREADS = 256;
-constexpr int QHIST_PER_THREAD = 16;    // elements per thread and grid stride
-
-// What a call computes: shapes checked by check_args.
-struct Shape {
-  int G = 0, C = 0, I = 0, W = 0;   // groups, chains, saved iterations, raw columns
-  int first = 0, n = 0, h = 0, m = 0;   // skipped, post-warmup, half length, split chains
-  int P = 0, np = 0, width = 0;     // output columns, probabilities, 5 + np
-  int64_t S = 0;                    // pooled draws of one column
-  OutModel model{};                 // lambda_scale: per group, in lscale
-  std::vector<double> lscale;
-};
-
-// `who` names the caller in the messages ("summary", "monitor"); the rank diagnostics take no
-// probabilities (with_probs false: n_probs and probs are not read, np = 0)
 int check_args(const std::string& who, bool with_probs, const fitoct_problem* probs, int n_groups,
                int chains, int iters_saved, const void* draws, const fitoct_summary_config* cfg,
                const double* out, Shape& s) {
@@ -93,7 +72,6 @@ int check_args(const std::string& who, bool with_probs, const fitoct_problem* pr
   return FITOCT_OK;
 }
 
-// the checks of a device route that need the runtime: the ordinal, and d_draws a device buffer
 int check_device(const std::string& who, const fitoct_summary_config* cfg, const void* d_draws) {
   if (cfg->device < 0) return fail(FITOCT_E_ARG, who + ": device is negative");
   int ndev = 0;
@@ -110,42 +88,72 @@ int check_device(const std::string& who, const fitoct_summary_config* cfg, const
   return FITOCT_OK;
 }
 
-// output column j of a raw row (7 sampler columns, then the parameter columns)
-FITOCT_HD inline double column_value(const OutModel& m, int j, const double* raw) {
-  return j < 7 ? raw[j] : out_value(m, out_spec(m, j - 7), raw + 7);
+// ---- where the last run's draws lie (plan_internal.h) ----------------------------------------
+fitoct_problem with_data(const fitoct_plan* pl) {
+  fitoct_problem p = pl->prob;
+  if (pl->h_xyu.size() == 3 * (size_t)p.N) {
+    p.x = pl->h_xyu.data();
+    p.y = p.x + p.N;
+    p.uy = p.y + p.N;
+  }
+  p.B = pl->h_B.empty() ? nullptr : pl->h_B.data();
+  return p;
 }
+
+int plan_where(fitoct_plan* pl, const char* needs, Where& w) {
+  if (pl->launched) return fail(FITOCT_E_ARG, "plan is running: call fitoct_plan_wait first");
+  if (!pl->ran) return fail(FITOCT_E_ARG, "plan has not run");
+  const bool group = !pl->shards.empty();
+  if (group && !pl->gather_dst)
+    return fail(FITOCT_E_ARG, std::string("the device-list run left its shards in per-device "
+                                          "buffers: pass a d_draws to the run, ") +
+                                  needs + " the draws in one buffer");
+  w.probs.push_back(with_data(pl));
+  w.chains = pl->kp.chains;
+  w.iters_saved = pl->kp.iters_saved;
+  w.device = group ? pl->gather_dev : pl->cfg.device;
+  w.draws = (const char*)(group ? pl->gather_dst : (void*)pl->last_draws);
+  return FITOCT_OK;
+}
+
+int batch_where(fitoct_batch* b, const char* needs, Where& w) {
+  if (!b->ran) return fail(FITOCT_E_ARG, "batch has not run");
+  const bool group = !b->subs.empty();
+  if (group && !b->gather_dst)
+    return fail(FITOCT_E_ARG, std::string("the device-list run left its files in per-device "
+                                          "buffers: pass a d_draws to the run, ") +
+                                  needs + " the draws in one buffer");
+  if (group) {
+    for (const fitoct_batch* sb : b->subs)
+      for (const fitoct_plan* pl : sb->plans) w.probs.push_back(with_data(pl));
+  } else {
+    for (const fitoct_plan* pl : b->plans) w.probs.push_back(with_data(pl));
+  }
+  const fitoct_plan* p0 = group ? b->subs[0]->plans[0] : b->plans[0];
+  w.chains = b->cfg.chains;
+  w.iters_saved = p0->kp.iters_saved;
+  w.device = group ? b->gather_dev : b->cfg.device;
+  w.draws = (const char*)(group ? b->gather_dst : (void*)p0->last_draws);
+  w.group_bytes = sizeof(double) * (size_t)w.chains * w.iters_saved *
+                  (model_dim(p0->prob.prior_type, p0->prob.Nn) + 8);
+  return FITOCT_OK;
+}
+
+namespace {
+
+constexpr int ACOV_WAVES = 4;
+constexpr int ACOV_TILE = 512;          // series elements per LDS tile and wave
+constexpr int QHIST_THREADS = 256;
+constexpr int QHIST_PER_THREAD = 16;    // elements per thread and grid stride
 
 // ---- kernels --------------------------------------------------------------------------------
-// What every kernel needs of the call (by value: a few words).
-struct KShape {
-  int G, C, I, W, first, n, h, m;
-  int c0, ncc;          // this pass: first output column and number of columns
-  OutModel model;
-};
-
-// X[pair = g * ncc + jc][chain][n]
-__device__ inline const double* chain_series(const double* X, const KShape& k, int64_t pair,
-                                             int chain) {
-  return X + ((size_t)pair * k.C + chain) * k.n;
-}
-
 // one workgroup per (group, chain, block of STAGE_ROWS rows)
 __global__ __launch_bounds__(STAGE_THREADS) void stage_kernel(KShape k, const double* draws,
                                                               const double* lscale, double* X) {
-  extern __shared__ double tile[];   // [STAGE_ROWS][Wp], Wp odd: rows land on different banks
+  extern __shared__ double tile[];   // [STAGE_ROWS][Wp]
   const int Wp = k.W | 1;
-  const int rblocks = (k.n + STAGE_ROWS - 1) / STAGE_ROWS;
-  int64_t b = blockIdx.x;
-  const int rb = (int)(b % rblocks);
-  b /= rblocks;
-  const int c = (int)(b % k.C), g = (int)(b / k.C);
-  const int i0 = rb * STAGE_ROWS, rows = min(STAGE_ROWS, k.n - i0);
-  const double* src = draws + (((size_t)g * k.C + c) * k.I + k.first + i0) * k.W;
-  for (int t = threadIdx.x; t < rows * k.W; t += STAGE_THREADS) {
-    const int r = t / k.W;
-    tile[r * Wp + (t - r * k.W)] = src[t];
-  }
-  __syncthreads();
+  const RowBlock rb = load_row_tile(k, draws, tile);
+  const int g = rb.g, c = rb.c, i0 = rb.i0, rows = rb.rows;
   OutModel m = k.model;
   m.lambda_scale = lscale[g];
   for (int t = threadIdx.x; t < k.ncc * STAGE_ROWS; t += STAGE_THREADS) {
@@ -317,80 +325,13 @@ __global__ __launch_bounds__(64) void qselect_kernel(QState q) {
   for (int i = t; i < QT_MAX * 256; i += 64) H[i] = 0ull;
 }
 
-// ---- device route ---------------------------------------------------------------------------
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
-    return FITOCT_OK;
-  }
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-// the calling thread's device is put back when the call returns
-struct DeviceKeep {
-  int dev = -1;
-  DeviceKeep() {
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  }
-  ~DeviceKeep() {
-    if (dev >= 0) (void)hipSetDevice(dev);
-  }
-};
 struct NeedLag {};   // Geyer's rule asked for a lag block that has not been computed yet
-
-#define FITOCT_TRY(expr)          \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_) return rc_;          \
-  } while (0)
-
-// Output columns per pass: as many as the staging cap holds at bytes_per_column each (never
-// less than one); the passes are c0 = 0, ncc_max, ... with min(ncc_max, P - c0) columns.
-inline int columns_per_pass(const Shape& s, const fitoct_summary_config* cfg,
-                            int64_t bytes_per_column) {
-  const int64_t cap = cfg->max_staging_bytes > 0 ? cfg->max_staging_bytes : DEFAULT_STAGING_BYTES;
-  return (int)std::max<int64_t>(1, std::min<int64_t>(s.P, cap / bytes_per_column));
-}
-
-// Device buffers of the moments and of Geyer's rounds, for up to pairs_max series sets.
-struct EssBufs {
-  DevBuf mom, flags, acov, act;
-  int alloc(int64_t pairs_max, int m) {
-    FITOCT_TRY(mom.alloc((size_t)pairs_max * m * 4 * sizeof(double)));
-    FITOCT_TRY(flags.alloc((size_t)pairs_max * m * sizeof(int)));
-    FITOCT_TRY(acov.alloc((size_t)pairs_max * LAG_BLOCK * sizeof(double)));
-    FITOCT_TRY(act.alloc((size_t)pairs_max * sizeof(int)));
-    return FITOCT_OK;
-  }
-};
-
-// moments_kernel over X[pairs][k.C][k.n] and its read-back, queued on st (not synchronised)
-inline int queue_moments(const KShape& k, const double* X, int64_t pairs, EssBufs& b,
-                         hipStream_t st, std::vector<double>& h_mom, std::vector<int>& h_flags) {
-  moments_kernel<<<dim3((unsigned)(pairs * k.m)), dim3(64), 0, st>>>(k, X, b.mom.as<double>(),
-                                                                     b.flags.as<int>());
-  HIP_TRY(hipGetLastError());
-  h_mom.resize((size_t)pairs * k.m * 4);
-  h_flags.resize((size_t)pairs * k.m);
-  HIP_TRY(hipMemcpyAsync(h_mom.data(), b.mom.p, sizeof(double) * h_mom.size(),
-                         hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(h_flags.data(), b.flags.p, sizeof(int) * h_flags.size(),
-                         hipMemcpyDeviceToHost, st));
-  return FITOCT_OK;
-}
 
 // Pooled mean and sd (n - 1) of one pair from the moments of its m split chains of h draws
 // (moments_kernel's rows mo[m][4]; S = m / 2 * n values): the sums are added in chain order,
 // the centred sums of squares combined by Chan et al.'s update; the middle draw of an odd n
 // is carried separately.
-inline void pooled_mean_sd(const double* mo, int n, int h, int m, int64_t S, double& mean,
-                           double& sd) {
+void pooled_mean_sd(const double* mo, int n, int h, int m, int64_t S, double& mean, double& sd) {
   double sum = 0.0;
   for (int j = 0; j < m; ++j) sum += mo[4 * j + 2];
   if (n & 1)
@@ -409,13 +350,42 @@ inline void pooled_mean_sd(const double* mo, int n, int h, int m, int64_t S, dou
   sd = sqrt(ssq / (double)(S - 1));
 }
 
-// n_eff of the pairs listed in `active` (ess[pair] is written): autocovariance in blocks of 64
-// lags, Geyer's rule (ess_moments) on the host block by block, the next block only for the
-// pairs that have not terminated.  h_mom: the moments of X (queue_moments, synchronised), still
-// in b.mom on the device.
-inline int ess_rounds(const KShape& k, const double* X, EssBufs& b, hipStream_t st,
-                      const std::vector<double>& h_mom, std::vector<int> active,
-                      std::vector<double>& ess) {
+}  // namespace
+
+// ---- what the users queue -------------------------------------------------------------------
+int queue_stage(const KShape& k, const void* d_draws, const double* lscale, double* X,
+                hipStream_t st) {
+  stage_kernel<<<dim3((unsigned)((int64_t)row_blocks(k.n) * k.C * k.G)), dim3(STAGE_THREADS),
+                 row_tile_bytes(k.W), st>>>(k, (const double*)d_draws, lscale, X);
+  HIP_TRY(hipGetLastError());
+  return FITOCT_OK;
+}
+
+int EssBufs::alloc(int64_t pairs_max, int m) {
+  FITOCT_TRY(mom.alloc((size_t)pairs_max * m * 4 * sizeof(double)));
+  FITOCT_TRY(flags.alloc((size_t)pairs_max * m * sizeof(int)));
+  FITOCT_TRY(acov.alloc((size_t)pairs_max * LAG_BLOCK * sizeof(double)));
+  FITOCT_TRY(act.alloc((size_t)pairs_max * sizeof(int)));
+  return FITOCT_OK;
+}
+
+int queue_moments(const KShape& k, const double* X, int64_t pairs, EssBufs& b, hipStream_t st,
+                  std::vector<double>& h_mom, std::vector<int>& h_flags) {
+  moments_kernel<<<dim3((unsigned)(pairs * k.m)), dim3(64), 0, st>>>(k, X, b.mom.as<double>(),
+                                                                     b.flags.as<int>());
+  HIP_TRY(hipGetLastError());
+  h_mom.resize((size_t)pairs * k.m * 4);
+  h_flags.resize((size_t)pairs * k.m);
+  HIP_TRY(hipMemcpyAsync(h_mom.data(), b.mom.p, sizeof(double) * h_mom.size(),
+                         hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(h_flags.data(), b.flags.p, sizeof(int) * h_flags.size(),
+                         hipMemcpyDeviceToHost, st));
+  return FITOCT_OK;
+}
+
+int ess_rounds(const KShape& k, const double* X, EssBufs& b, hipStream_t st,
+               const std::vector<double>& h_mom, std::vector<int> active,
+               std::vector<double>& ess) {
   std::vector<std::vector<double>> lags(active.size());   // lag blocks computed so far
   std::vector<int> slot(active.size());                   // active[a]'s entry of lags
   for (size_t a = 0; a < active.size(); ++a) slot[a] = (int)a;
@@ -434,11 +404,7 @@ inline int ess_rounds(const KShape& k, const double* X, EssBufs& b, hipStream_t 
     for (size_t a = 0; a < active.size(); ++a) {
       std::vector<double>& ac = lags[slot[a]];
       ac.insert(ac.end(), h_acov.begin() + a * LAG_BLOCK, h_acov.begin() + (a + 1) * LAG_BLOCK);
-      const double* mo = h_mom.data() + (size_t)active[a] * k.m * 4;
-      for (int j = 0; j < k.m; ++j) {
-        cm[j] = mo[4 * j];
-        cv[j] = mo[4 * j + 1] / (k.h - 1);
-      }
+      split_moments(h_mom.data() + (size_t)active[a] * k.m * 4, k.m, k.h, cm.data(), cv.data());
       try {
         ess[active[a]] = ess_moments(cm.data(), cv.data(), k.m, k.h, [&](int lag) {
           if (lag >= k.h) return 0.0;
@@ -457,44 +423,35 @@ inline int ess_rounds(const KShape& k, const double* X, EssBufs& b, hipStream_t 
 }
 
 // ---- exact radix select (qhist_kernel / qselect_kernel) -------------------------------------
-// Device buffers of the select, for up to pairs_max pairs.
-struct SelectBufs {
-  DevBuf hist, rank, pre, slot, uniq, nuniq;
-  int alloc(int64_t pairs_max) {
-    FITOCT_TRY(hist.alloc((size_t)pairs_max * QT_MAX * 256 * sizeof(unsigned long long)));
-    FITOCT_TRY(rank.alloc((size_t)pairs_max * QT_MAX * sizeof(long long)));
-    FITOCT_TRY(pre.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
-    FITOCT_TRY(slot.alloc((size_t)pairs_max * QT_MAX * sizeof(int)));
-    FITOCT_TRY(uniq.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
-    FITOCT_TRY(nuniq.alloc((size_t)pairs_max * sizeof(int)));
-    return FITOCT_OK;
+int SelectBufs::alloc(int64_t pairs_max) {
+  FITOCT_TRY(hist.alloc((size_t)pairs_max * QT_MAX * 256 * sizeof(unsigned long long)));
+  FITOCT_TRY(rank.alloc((size_t)pairs_max * QT_MAX * sizeof(long long)));
+  FITOCT_TRY(pre.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
+  FITOCT_TRY(slot.alloc((size_t)pairs_max * QT_MAX * sizeof(int)));
+  FITOCT_TRY(uniq.alloc((size_t)pairs_max * QT_MAX * sizeof(unsigned long long)));
+  FITOCT_TRY(nuniq.alloc((size_t)pairs_max * sizeof(int)));
+  return FITOCT_OK;
+}
+
+SelectRanks::SelectRanks(const Shape& s, const fitoct_summary_config* cfg, int64_t pairs_max)
+    : qidx(s.np), rank0((size_t)pairs_max * QT_MAX, 0), one((size_t)pairs_max, 1) {
+  for (int i = 0; i < s.np; ++i) {
+    qidx[i] = quantile_index(s.S, cfg->probs[i]);
+    for (int64_t p = 0; p < pairs_max; ++p) {
+      rank0[p * QT_MAX + 2 * i] = qidx[i].lo;
+      rank0[p * QT_MAX + 2 * i + 1] = qidx[i].hi;
+    }
   }
-};
-// The order statistics every pair needs, x[lo] and x[hi] of each probability, as the initial
-// ranks of up to pairs_max pairs (and the one distinct prefix every pair starts with).
-struct SelectRanks {
-  std::vector<long long> rank0;
-  std::vector<int> one;
-  SelectRanks(const std::vector<QIndex>& qidx, int64_t pairs_max)
-      : rank0((size_t)pairs_max * QT_MAX, 0), one((size_t)pairs_max, 1) {
-    for (size_t i = 0; i < qidx.size(); ++i)
-      for (int64_t p = 0; p < pairs_max; ++p) {
-        rank0[p * QT_MAX + 2 * i] = qidx[i].lo;
-        rank0[p * QT_MAX + 2 * i + 1] = qidx[i].hi;
-      }
-  }
-};
-// workgroups of qhist_kernel per pair
-inline int qhist_blocks(int64_t S) {
+}
+
+int qhist_blocks(int64_t S) {
   return (int)std::max<int64_t>(
       1, std::min<int64_t>(1024, (S + QHIST_THREADS * QHIST_PER_THREAD - 1) /
                                      (QHIST_THREADS * QHIST_PER_THREAD)));
 }
-// The eight passes over X[pairs][S] for T targets per pair and the read-back of the selected
-// keys h_keys[pairs][QT_MAX], queued on st (not synchronised).
-inline int queue_select(const double* X, int64_t pairs, int64_t S, int T, int nblk,
-                        const SelectBufs& b, const SelectRanks& r, hipStream_t st,
-                        std::vector<unsigned long long>& h_keys) {
+
+int queue_select(const double* X, int64_t pairs, int64_t S, int T, int nblk, const SelectBufs& b,
+                 const SelectRanks& r, hipStream_t st, std::vector<unsigned long long>& h_keys) {
   QState qs{T, S, b.hist.as<unsigned long long>(), b.rank.as<long long>(),
             b.pre.as<unsigned long long>(), b.slot.as<int>(), b.uniq.as<unsigned long long>(),
             b.nuniq.as<int>()};
@@ -518,5 +475,22 @@ inline int queue_select(const double* X, int64_t pairs, int64_t S, int T, int nb
   return FITOCT_OK;
 }
 
-}  // namespace
+// ---- rows -----------------------------------------------------------------------------------
+bool pair_row(const Shape& s, int64_t p, const std::vector<double>& h_mom,
+              const std::vector<int>& h_flags, const std::vector<unsigned long long>& h_keys,
+              const SelectRanks& r, bool nan, double* row, int width, int sd_at, bool* constant) {
+  int fl = nan ? 1 : 0;
+  for (int j = 0; j < s.m; ++j) fl |= h_flags[(size_t)p * s.m + j];
+  if (constant) *constant = !(fl & 2);
+  if (fl & 1) {
+    for (int i = 0; i < width; ++i) row[i] = NAN;
+    return false;
+  }
+  pooled_mean_sd(h_mom.data() + (size_t)p * s.m * 4, s.n, s.h, s.m, s.S, row[0], row[sd_at]);
+  for (int i = 0; i < s.np; ++i)
+    row[sd_at + 1 + i] = quantile_lerp(key_value(h_keys[p * QT_MAX + 2 * i]),
+                                       key_value(h_keys[p * QT_MAX + 2 * i + 1]), r.qidx[i].frac);
+  return true;
+}
+
 }  // namespace fitoct

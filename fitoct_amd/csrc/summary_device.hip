@@ -4,50 +4,30 @@
 // buffer, and the same computation on the host (fitoct_summary_host, on top of
 // split_rhat_ess and std::nth_element) that the device route is tested against.
 //
-// Device route, per pass over a chunk of output columns (the first three kernels and Geyer's
-// rounds live in summary_kernels.h, shared with monitor_device.hip):
-//   stage_kernel    raw rows (contiguous, read coalesced through LDS) -> the output-layout
-//                   transform (summary_shared.h, the copy stan_output.cpp uses) -> a
-//                   column-major post-warmup staging buffer X[group][col][chain][n];
-//   moments_kernel  one wave per (group, col, split chain): mean, then centred sum of
-//                   squares, NaN and constant flags (butterfly reductions: a fixed order);
-//   acov_kernel     per (group, col, block of 64 lags): biased autocovariance of every split
-//                   chain about its own mean, averaged over the split chains in a fixed
-//                   order.  The host applies Geyer's rule (ess_moments, shared with the host
-//                   diagnostics) block by block and asks for the next block only for the
-//                   columns that have not terminated;
-//   qhist_kernel /  exact radix select over order-preserving 64-bit keys of the pooled
-//   qselect_kernel  values: eight 8-bit passes, most significant byte first, for the up to
-//                   2 n_probs order statistics of each (group, col) at once; histograms in
-//                   LDS, merged with integer atomics; a one-wave kernel picks the digits.
-// No floating-point atomics anywhere: the results are the same bit for bit from call to call.
-#include <hip/hip_runtime.h>
-
-#include <math.h>
-#include <stdint.h>
-
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "fitoct.h"
-#include "host_internal.h"
-#include "plan_internal.h"
-#include "summary_kernels.h"
-#include "summary_shared.h"
+// Device route, per pass over a chunk of output columns, all of it the shared layer's
+// (posterior_common.hip, which describes the kernels): queue_stage, queue_moments, queue_select
+// for the quantiles, then on the host pair_row (a NaN row, or mean, sd and the quantiles), Rhat
+// from the split chains' moments, and ess_rounds for n_eff.  This file launches no kernel of
+// its own.  No floating-point atomics anywhere: the results are the same bit for bit from call
+// to call.
+#include "posterior_common.h"
 
 namespace fitoct {
 namespace {
 
-// out row = mean, se_mean, sd, the quantiles, n_eff, Rhat
+// out row = mean, se_mean, sd, the quantiles, n_eff, Rhat; put_tail: what needs n_eff, once
+// mean, sd and the quantiles stand in the row
+void put_tail(const Shape& s, double* row, double ess, double rhat) {
+  row[1] = ess > 0.0 ? row[2] / sqrt(ess) : NAN;
+  row[3 + s.np] = ess;
+  row[4 + s.np] = rhat;
+}
 void put_row(const Shape& s, double* row, double mean, double sd, const double* q, double ess,
              double rhat) {
   row[0] = mean;
-  row[1] = ess > 0.0 ? sd / sqrt(ess) : NAN;
   row[2] = sd;
   for (int i = 0; i < s.np; ++i) row[3 + i] = q[i];
-  row[3 + s.np] = ess;
-  row[4 + s.np] = rhat;
+  put_tail(s, row, ess, rhat);
 }
 void nan_row(const Shape& s, double* row) {
   for (int i = 0; i < s.width; ++i) row[i] = NAN;
@@ -103,22 +83,17 @@ int summary_host(const Shape& s, const double* draws, const fitoct_summary_confi
   return FITOCT_OK;
 }
 
-// ---- kernels: stage_kernel, moments_kernel, acov_kernel, qhist_kernel, qselect_kernel
-// (summary_kernels.h, shared with monitor_device.hip and curves_device.hip) ------------------
-
 // ---- device route ---------------------------------------------------------------------------
 int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_config* cfg,
                    hipStream_t st, double* out) {
   DeviceKeep keep;
   HIP_TRY(hipSetDevice(cfg->device));
   const int64_t col_bytes = (int64_t)s.G * s.S * (int64_t)sizeof(double);
-  const int ncc_max = columns_per_pass(s, cfg, col_bytes);
+  const int ncc_max = (int)items_per_pass(cfg, s.P, col_bytes);
   const int64_t pairs_max = (int64_t)s.G * ncc_max;
-  const int rblocks = (s.n + STAGE_ROWS - 1) / STAGE_ROWS;
   const int nblk = qhist_blocks(s.S);
   const int64_t limit = (int64_t)1 << 31;
-  if ((int64_t)rblocks * s.C * s.G >= limit || pairs_max * s.m >= limit ||
-      pairs_max * nblk >= limit)
+  if (row_grid(s) >= limit || pairs_max * s.m >= limit || pairs_max * nblk >= limit)
     return fail(FITOCT_E_ARG, "summary: shape too large for one launch (lower max_staging_bytes)");
   const int T = 2 * s.np;
 
@@ -130,69 +105,41 @@ int summary_device(const Shape& s, const void* d_draws, const fitoct_summary_con
   FITOCT_TRY(lscale.alloc((size_t)s.G * sizeof(double)));
   if (T > 0) FITOCT_TRY(sel.alloc(pairs_max));
   HIP_TRY(hipMemcpyAsync(lscale.p, s.lscale.data(), sizeof(double) * s.G, hipMemcpyHostToDevice, st));
+  const SelectRanks ranks(s, cfg, pairs_max);
 
-  // the order statistics every column needs: x[lo], x[hi] of each probability
-  std::vector<QIndex> qidx(s.np);
-  for (int i = 0; i < s.np; ++i) qidx[i] = quantile_index(s.S, cfg->probs[i]);
-  const SelectRanks ranks(qidx, pairs_max);
-
-  std::vector<double> h_mom, cm(s.m), cv(s.m), q((size_t)std::max(1, s.np));
+  std::vector<double> h_mom, cm(s.m), cv(s.m);
   std::vector<int> h_flags;
   std::vector<unsigned long long> h_keys;
   for (int c0 = 0; c0 < s.P; c0 += ncc_max) {
     const int ncc = std::min(ncc_max, s.P - c0);
     const int64_t pairs = (int64_t)s.G * ncc;
-    KShape k{s.G, s.C, s.I, s.W, s.first, s.n, s.h, s.m, c0, ncc, s.model};
-    stage_kernel<<<dim3((unsigned)((int64_t)rblocks * s.C * s.G)), dim3(STAGE_THREADS),
-                   sizeof(double) * STAGE_ROWS * (s.W | 1), st>>>(
-        k, (const double*)d_draws, lscale.as<double>(), X.as<double>());
-    HIP_TRY(hipGetLastError());
+    const KShape k = kshape(s, c0, ncc);
+    FITOCT_TRY(queue_stage(k, d_draws, lscale.as<double>(), X.as<double>(), st));
     FITOCT_TRY(queue_moments(k, X.as<double>(), pairs, eb, st, h_mom, h_flags));
-
-    // quantiles: queued behind the moments, read back after the autocovariance rounds
+    // quantiles: queued behind the moments
     if (T > 0) FITOCT_TRY(queue_select(X.as<double>(), pairs, s.S, T, nblk, sel, ranks, st, h_keys));
     HIP_TRY(hipStreamSynchronize(st));
 
-    // per pair: NaN / constant pattern, pooled mean and sd, Rhat; which pairs need n_eff
-    struct Col {
-      double mean = NAN, sd = NAN, rhat = NAN;
-      bool has_nan = false, constant = false;
+    // per pair: a NaN row, or mean, sd and the quantiles; Rhat; which pairs need n_eff
+    auto row_of = [&](int64_t p) {
+      return out + ((size_t)(p / ncc) * s.P + c0 + (int)(p % ncc)) * s.width;
     };
-    std::vector<Col> cols((size_t)pairs);
+    std::vector<double> rhat((size_t)pairs, NAN), ess((size_t)pairs, NAN);
+    std::vector<char> has_nan((size_t)pairs, 0);
     std::vector<int> active;
     for (int64_t p = 0; p < pairs; ++p) {
-      Col& c = cols[p];
-      const double* mo = h_mom.data() + (size_t)p * s.m * 4;
-      int fl = 0;
-      for (int j = 0; j < s.m; ++j) fl |= h_flags[(size_t)p * s.m + j];
-      c.has_nan = fl & 1;
-      c.constant = !(fl & 2);
-      if (c.has_nan) continue;
-      pooled_mean_sd(mo, s.n, s.h, s.m, s.S, c.mean, c.sd);
-      if (c.constant) continue;   // n_eff and Rhat are NaN (split_rhat_ess)
-      for (int j = 0; j < s.m; ++j) {
-        cm[j] = mo[4 * j];
-        cv[j] = mo[4 * j + 1] / (s.h - 1);
-      }
-      c.rhat = psr_moments(cm.data(), cv.data(), s.m, s.h);
+      bool constant = false;
+      has_nan[p] = !pair_row(s, p, h_mom, h_flags, h_keys, ranks, false, row_of(p), s.width, 2,
+                             &constant);
+      if (has_nan[p] || constant) continue;   // constant: n_eff and Rhat are NaN (split_rhat_ess)
+      split_moments(h_mom.data() + (size_t)p * s.m * 4, s.m, s.h, cm.data(), cv.data());
+      rhat[p] = psr_moments(cm.data(), cv.data(), s.m, s.h);
       active.push_back((int)p);
     }
     // n_eff: autocovariance in blocks of 64 lags, only for the columns still undecided
-    std::vector<double> ess((size_t)pairs, NAN);
     FITOCT_TRY(ess_rounds(k, X.as<double>(), eb, st, h_mom, active, ess));
-    for (int64_t p = 0; p < pairs; ++p) {
-      const int g = (int)(p / ncc), j = c0 + (int)(p % ncc);
-      double* row = out + ((size_t)g * s.P + j) * s.width;
-      const Col& c = cols[p];
-      if (c.has_nan) {
-        nan_row(s, row);
-        continue;
-      }
-      for (int i = 0; i < s.np; ++i)
-        q[i] = quantile_lerp(key_value(h_keys[p * QT_MAX + 2 * i]),
-                             key_value(h_keys[p * QT_MAX + 2 * i + 1]), qidx[i].frac);
-      put_row(s, row, c.mean, c.sd, q.data(), ess[p], c.rhat);
-    }
+    for (int64_t p = 0; p < pairs; ++p)
+      if (!has_nan[p]) put_tail(s, row_of(p), ess[p], rhat[p]);
   }
   return FITOCT_OK;
 }
@@ -247,41 +194,24 @@ int32_t fitoct_summary_device(const fitoct_problem* probs, int32_t n_groups, int
 int32_t fitoct_plan_summary(fitoct_plan* pl, const fitoct_summary_config* cfg, double* out) {
   return guarded(__func__, [&]() -> int32_t {
     if (!pl || !cfg || !out) return fail(FITOCT_E_ARG, "summary: NULL argument");
-    if (pl->launched)
-      return fail(FITOCT_E_ARG, "plan is running: call fitoct_plan_wait first");
-    if (!pl->ran) return fail(FITOCT_E_ARG, "plan has not run");
-    const bool group = !pl->shards.empty();
-    if (group && !pl->gather_dst)
-      return fail(FITOCT_E_ARG, "the device-list run left its shards in per-device buffers: pass "
-                                "a d_draws to the run, the summary needs the draws in one buffer");
+    Where w;
+    FITOCT_TRY(plan_where(pl, "the summary needs", w));
     fitoct_summary_config c = *cfg;
-    c.device = group ? pl->gather_dev : pl->cfg.device;
-    return summary_device_checked(&pl->prob, 1, pl->kp.chains, pl->kp.iters_saved,
-                                  group ? pl->gather_dst : (void*)pl->last_draws, &c, nullptr, out);
+    c.device = w.device;
+    return summary_device_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, &c, nullptr,
+                                  out);
   });
 }
 
 int32_t fitoct_batch_summary(fitoct_batch* b, const fitoct_summary_config* cfg, double* out) {
   return guarded(__func__, [&]() -> int32_t {
     if (!b || !cfg || !out) return fail(FITOCT_E_ARG, "summary: NULL argument");
-    if (!b->ran) return fail(FITOCT_E_ARG, "batch has not run");
-    const bool group = !b->subs.empty();
-    if (group && !b->gather_dst)
-      return fail(FITOCT_E_ARG, "the device-list run left its files in per-device buffers: pass "
-                                "a d_draws to the run, the summary needs the draws in one buffer");
-    std::vector<fitoct_problem> probs;
-    if (group) {
-      for (const fitoct_batch* sb : b->subs)
-        for (const fitoct_plan* pl : sb->plans) probs.push_back(pl->prob);
-    } else {
-      for (const fitoct_plan* pl : b->plans) probs.push_back(pl->prob);
-    }
-    const fitoct_plan* p0 = group ? b->subs[0]->plans[0] : b->plans[0];
+    Where w;
+    FITOCT_TRY(batch_where(b, "the summary needs", w));
     fitoct_summary_config c = *cfg;
-    c.device = group ? b->gather_dev : b->cfg.device;
-    return summary_device_checked(probs.data(), (int32_t)probs.size(), b->cfg.chains,
-                                  p0->kp.iters_saved,
-                                  group ? b->gather_dst : (void*)p0->last_draws, &c, nullptr, out);
+    c.device = w.device;
+    return summary_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains, w.iters_saved,
+                                  w.draws, &c, nullptr, out);
   });
 }
 

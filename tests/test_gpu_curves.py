@@ -86,6 +86,16 @@ def test_summary_table_is_unchanged():
     assert _bits(table).tobytes() == _bits(want).tobytes()
 
 
+def test_curves_table_is_unchanged(cases):
+    """The curves' raw-row load, moments, select and row forming moved into the shared layer:
+    the device table of case b, in one pass, is the bytes recorded before the move
+    (tests/golden/record_posterior.py)."""
+    table = _device_table(cases["b"])
+    want = np.load(os.path.join(GOLDEN, "curves_case_b.npy"))
+    assert table.shape == want.shape
+    assert _bits(table).tobytes() == _bits(want).tobytes()
+
+
 # ---- real runs ----------------------------------------------------------------------------------
 def _prob(prior, N, Nn, seed=3):
     t0, S0 = default_prior()

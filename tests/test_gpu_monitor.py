@@ -7,6 +7,7 @@ buffer a run can leave its draws in, and the refusals that come before any kerne
 from __future__ import annotations
 
 import dataclasses
+import os
 
 import numpy as np
 import pytest
@@ -21,6 +22,7 @@ from fitoct_amd.synth import default_prior, synth_decay
 
 pytestmark = pytest.mark.gpu
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 @pytest.fixture(scope="module")
 def cases():
@@ -71,6 +73,17 @@ def test_column_passes_do_not_change_a_bit(cases, name):
     assert _bits(three).tobytes() == _bits(one).tobytes()
     each = _device_table(case, max_staging_bytes=1)   # never less than one column per pass
     assert _bits(each).tobytes() == _bits(one).tobytes()
+
+
+@pytest.mark.parametrize("name", ["a", "i"])
+def test_monitor_table_is_unchanged(cases, name):
+    """The staging, moments and autocovariance kernels moved into the shared layer's one
+    translation unit: the device table, in both sort regimes, is the bytes recorded before the
+    move (tests/golden/record_posterior.py)."""
+    table = _device_table(cases[name])
+    want = np.load(os.path.join(GOLDEN, f"monitor_case_{name}.npy"))
+    assert table.shape == want.shape
+    assert _bits(table).tobytes() == _bits(want).tobytes()
 
 
 # ---- real runs ----------------------------------------------------------------------------------
