@@ -125,6 +125,21 @@ class SummaryConfig(C.Structure):
 
 MAX_PROBS = 16   # include/fitoct.h fitoct_summary_config.probs
 
+
+class PairsConfig(C.Structure):
+    _fields_ = [
+        ("first_iter", C.c_int32), ("n_cols", C.c_int32), ("cols", C.c_int32 * 64),
+        ("n_bins", C.c_int32), ("planes", C.c_int32), ("range_probs", C.c_double * 2),
+        ("log_mask", C.c_uint64), ("max_staging_bytes", C.c_int64), ("device", C.c_int32),
+    ]
+
+
+class PairsOut(C.Structure):
+    _fields_ = [("edges", _dp), ("hist1", _lp), ("outside", _lp), ("hist2", _lp), ("corr", _dp)]
+
+
+MAX_PAIRS_COLS = 64   # include/fitoct.h fitoct_pairs_config.cols
+
 CURVE = {"dL": 1, "m": 2, "resid": 4}   # include/fitoct.h FITOCT_CURVE_*
 
 TERMINATION = {0: "success", 10: "absolute parameter change", 20: "absolute objective change",
@@ -227,6 +242,16 @@ SIGNATURES = [
      [C.c_void_p, C.POINTER(SummaryConfig), C.c_int32, _lp, _dp, _dp]),
     ("fitoct_batch_curves_pick_params", C.c_int32,
      [C.c_void_p, C.c_int32, C.POINTER(SummaryConfig), C.c_int32, _lp, _dp, _dp]),
+    ("fitoct_default_pairs_config", None, [C.POINTER(PairsConfig)]),
+    ("fitoct_pairs_sizes", C.c_int32, [C.POINTER(PairsConfig), C.c_int32, _lp]),
+    ("fitoct_pairs_device", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, C.c_void_p, _dp,
+      C.POINTER(PairsConfig), C.c_void_p, C.POINTER(PairsOut)]),
+    ("fitoct_pairs_host", C.c_int32,
+     [C.POINTER(Problem), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.POINTER(PairsConfig),
+      C.POINTER(PairsOut)]),
+    ("fitoct_plan_pairs", C.c_int32, [C.c_void_p, _dp, C.POINTER(PairsConfig), C.POINTER(PairsOut)]),
+    ("fitoct_batch_pairs", C.c_int32, [C.c_void_p, _dp, C.POINTER(PairsConfig), C.POINTER(PairsOut)]),
 ]
 
 _LIB = None

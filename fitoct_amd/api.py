@@ -422,6 +422,153 @@ def monitor_host(draws: np.ndarray, prob, first_iter: int = 0) -> np.ndarray:
     return out
 
 
+PAIRS_PARS = ("theta", "yGP", "lambda", "sigma", "br", "lp__")   # plotExpGP.R:41's pars
+PAIRS_WHAT = ("edges", "hist", "outside", "panels", "corr")
+
+
+def _pairs_config(prob: ExpGPProblem, first_iter, pars, n_bins, planes, range_probs, log,
+                  max_staging_bytes=0, device=0):
+    """(``fitoct_pairs_config``, names of the selected columns): ``pars`` and ``log`` select
+    names or base names as :func:`_select_columns` does; the default ``pars`` are
+    plotExpGP.R:41's, those the family has."""
+    from .stanfit import _base
+    names, _ = _select_columns(prob, None)
+    if pars is None:
+        pars = [p for p in PAIRS_PARS if any(c == p or _base(c) == p for c in names)]
+    _, sel = _select_columns(prob, pars)
+    if not 1 <= len(sel) <= _lib.MAX_PAIRS_COLS:
+        raise ValueError(f"pairs takes 1..{_lib.MAX_PAIRS_COLS} columns, pars selects {len(sel)}")
+    _, logsel = _select_columns(prob, log) if len(log) else (names, [])   # (those among pars)
+    c = _lib.PairsConfig()
+    lib().fitoct_default_pairs_config(C.byref(c))
+    c.first_iter, c.n_cols = int(first_iter), len(sel)
+    for j, i in enumerate(sel):
+        c.cols[j] = i
+        if i in logsel:
+            c.log_mask |= 1 << j
+    c.n_bins, c.planes = int(n_bins), int(planes)
+    c.range_probs[0], c.range_probs[1] = float(range_probs[0]), float(range_probs[1])
+    c.max_staging_bytes, c.device = int(max_staging_bytes), int(device)
+    return c, [names[i] for i in sel]
+
+
+def _pairs_ranges(ranges, columns, groups):
+    """``ranges`` as ``[groups, n_cols, 2]`` (NaN: automatic) or None: an array of that shape
+    (``[n_cols, 2]`` for every group), or ``{column name: (lo, hi)}``."""
+    if ranges is None:
+        return None
+    if isinstance(ranges, dict):
+        unknown = set(ranges) - set(columns)
+        if unknown:
+            raise KeyError(f"ranges names columns that pars does not select: {sorted(unknown)}")
+        ranges = [ranges.get(n, (np.nan, np.nan)) for n in columns]
+    r = np.asarray(ranges, dtype=np.float64)
+    r = np.ascontiguousarray(np.broadcast_to(r, (groups, len(columns), 2)))
+    return r
+
+
+def _pairs_call(c, columns, groups, S, ranges, what, call) -> dict:
+    """Allocate what ``what`` names of a pairs table, run ``call(ranges, config, out)`` (one of
+    the ``fitoct_*pairs*`` entries) and return the arrays over the groups."""
+    bad = [w for w in what if w not in PAIRS_WHAT]
+    if bad or not len(what):
+        raise ValueError(f"what must name some of {PAIRS_WHAT}, got {what!r}")
+    nc, nb, pl = c.n_cols, c.n_bins, c.planes
+    shapes = {"edges": (groups, nc, nb + 1), "hist": (groups, nc, pl, nb), "outside": (groups, nc, 2),
+              "panels": (groups, nc * (nc - 1) // 2, pl, nb, nb), "corr": (groups, nc, nc)}
+    t = {w: np.empty(shapes[w], dtype=np.float64 if w in ("edges", "corr") else np.int64)
+         for w in PAIRS_WHAT if w in what}
+    o = _lib.PairsOut()
+    o.edges, o.corr = dptr(t.get("edges")), dptr(t.get("corr"))
+    for field_, w in (("hist1", "hist"), ("outside", "outside"), ("hist2", "panels")):
+        if w in t:
+            setattr(o, field_, t[w].ctypes.data_as(_lib._lp))
+    r = _pairs_ranges(ranges, columns, groups)
+    check(call(dptr(r), C.byref(c), C.byref(o)))
+    t["columns"], t["S"] = list(columns), int(S)
+    return t
+
+
+def pairs_rows(tables: dict, g: int = 0) -> dict:
+    """Group ``g`` of a pairs table (:func:`pairs_device`, :func:`pairs_host`) as the dict
+    :meth:`Plan.pairs` returns: ``{"columns": [...], "edges": [n_cols, nb + 1], "hist": [n_cols,
+    planes, nb], "outside": [n_cols, 2], "panels": {(name_a, name_b): [planes, nb, nb]}, "corr":
+    [n_cols, n_cols], "S": S}`` (the parts that were asked for)."""
+    cols = tables["columns"]
+    rows = {"columns": list(cols)}
+    for w in ("edges", "hist", "outside", "corr"):
+        if w in tables:
+            rows[w] = tables[w][g]
+    if "panels" in tables:
+        names = [(a, b) for i, a in enumerate(cols) for b in cols[i + 1:]]
+        rows["panels"] = {ab: tables["panels"][g][i] for i, ab in enumerate(names)}
+    rows["S"] = tables["S"]
+    return rows
+
+
+def pairs_device(d_draws: int, prob, chains: int, iters_saved: int, first_iter: int = 0,
+                 pars=None, n_bins: int = 32, planes: int = 1, range_probs=(0, 1), ranges=None,
+                 log=(), what=PAIRS_WHAT, max_staging_bytes: int = 0, device: int = 0,
+                 stream: int = 0) -> dict:
+    """The pairs plot of draws that lie in device memory (``fitoct_pairs_device``; ``d_draws``,
+    ``prob`` as :func:`summary_device`): per selected column the bin edges, the marginal
+    histogram and the counts outside the range, per couple of columns the joint histogram, and
+    the correlation matrix, over the pooled post-warmup draws; ``planes=2`` adds a second count
+    plane of the divergent draws.  ``ranges``: explicit ``(lo, hi)`` per column (see
+    :func:`_pairs_ranges`), else the quantiles at ``range_probs``; ``log`` names the columns
+    with geometric edges.  Returns the arrays over the groups (one group: :func:`pairs_rows`)."""
+    ps, arr = _problem_array(prob)
+    c, columns = _pairs_config(ps[0], first_iter, pars, n_bins, planes, range_probs, log,
+                               max_staging_bytes, device)
+    return _pairs_call(c, columns, len(ps), int(chains) * (int(iters_saved) - int(first_iter)),
+                       ranges, what,
+                       lambda r, cp, op: lib().fitoct_pairs_device(
+                           arr, len(ps), int(chains), int(iters_saved), C.c_void_p(d_draws or None),
+                           r, cp, C.c_void_p(stream or None), op))
+
+
+def pairs_host(draws: np.ndarray, prob, first_iter: int = 0, pars=None, n_bins: int = 32,
+               planes: int = 1, range_probs=(0, 1), ranges=None, log=(), what=PAIRS_WHAT) -> dict:
+    """The same table computed on the host (``fitoct_pairs_host``) from raw draws
+    ``[chains, iters_saved, n_cols]`` or ``[groups, chains, iters_saved, n_cols]``."""
+    ps, arr = _problem_array(prob)
+    draws = _host_draws(draws, ps)
+    c, columns = _pairs_config(ps[0], first_iter, pars, n_bins, planes, range_probs, log)
+    return _pairs_call(c, columns, len(ps), draws.shape[1] * (draws.shape[2] - int(first_iter)),
+                       ranges, what,
+                       lambda r, cp, op: lib().fitoct_pairs_host(
+                           arr, len(ps), draws.shape[1], draws.shape[2], dptr(draws), r, cp, op))
+
+
+def pripost_marginals(prior, posterior, pars=None, n_bins: int = 32,
+                      range_probs=(0.005, 0.995)) -> dict:
+    """What ``FitOCTLib::plotPriPostAll(prior fit, posterior fit)`` draws (priPost.R:22): per
+    column both runs have (``br`` is absent from a prior run), common bin edges and the two
+    marginal count vectors.  ``prior`` and ``posterior`` are handles with a completed run
+    (:class:`Plan`, or :class:`fitoct_amd.stanfit.StanFit`): each is asked for its automatic
+    ranges at ``range_probs``, then both are binned over the union.  Returns ``{name: {"edges":
+    [nb + 1], "prior": [nb], "posterior": [nb], "prior_outside": (below, above),
+    "posterior_outside": ...}}``."""
+    auto = [h.pairs(pars=pars, n_bins=n_bins, range_probs=range_probs, what=("edges",))
+            for h in (prior, posterior)]
+    common = [n for n in auto[0]["columns"] if n in auto[1]["columns"]]
+    ranges = {}
+    for n in common:
+        e = [a["edges"][a["columns"].index(n)] for a in auto]
+        ranges[n] = (np.fmin(e[0][0], e[1][0]), np.fmax(e[0][-1], e[1][-1]))   # NaN: no grid there
+    both = [h.pairs(pars=common, n_bins=n_bins, ranges=ranges, what=("edges", "hist", "outside"))
+            for h in (prior, posterior)]
+    if both[0]["edges"].tobytes() != both[1]["edges"].tobytes():   # one builder, the same ranges
+        raise RuntimeError("pripost_marginals: the two runs' edges differ")
+    out = {}
+    for j, n in enumerate(common):
+        out[n] = {"edges": both[1]["edges"][j]}
+        for side, t in zip(("prior", "posterior"), both):
+            out[n][side] = t["hist"][j, 0]
+            out[n][side + "_outside"] = tuple(int(v) for v in t["outside"][j])
+    return out
+
+
 @dataclass
 class SampleOutput:
     draws: np.ndarray          # [chains, iters_saved, n_cols]
@@ -473,6 +620,16 @@ class _LastRun:
         check(self._entry("curves")(self._h, bits, C.byref(c), dptr(out)))
         blocks = curves_blocks(out, self._probs, bits, probs)
         return self._each(problem, lambda p: curves_rows(blocks[p], self._probs[p], bits, probs))
+
+    def _pairs(self, problem, chains, pars, n_bins, planes, range_probs, ranges, log, what,
+               first_iter, max_staging_bytes):
+        first_iter = _post_warmup(self.cfg, first_iter)
+        c, columns = _pairs_config(self._probs[0], first_iter, pars, n_bins, planes, range_probs,
+                                   log, max_staging_bytes)
+        t = _pairs_call(c, columns, len(self._probs),
+                        chains * (self.info["iters_saved"] - first_iter), ranges, what,
+                        lambda r, cp, op: self._entry("pairs")(self._h, r, cp, op))
+        return self._each(problem, lambda p: pairs_rows(t, p))
 
     def _curves_pick(self, problem, chains, draws, n, seed, first_iter, *lead):
         """``lead``: what the pick entries take between the handle and the config."""
@@ -612,6 +769,17 @@ class Plan(_LastRun):
         ``first_iter`` defaults to the saved warmup."""
         return self._curves(0, what, probs, first_iter, max_staging_bytes)
 
+    def pairs(self, pars=None, n_bins: int = 32, planes: int = 1, range_probs=(0, 1),
+              ranges=None, log=(), what=PAIRS_WHAT, first_iter=None,
+              max_staging_bytes: int = 0) -> dict:
+        """The pairs plot of the last run (``pairs(fit, pars)``, ``SAPlot``), computed on the
+        device from the draws where they lie: the dict of :func:`pairs_rows` -- bin edges,
+        marginal and joint histograms (``planes=2``: a second plane of the divergent draws) and
+        the correlation matrix of the columns ``pars`` selects (default: plotExpGP.R:41's).
+        Arguments as :func:`pairs_device`; ``first_iter`` defaults to the saved warmup."""
+        return self._pairs(0, self.info["chains"], pars, n_bins, planes, range_probs, ranges, log,
+                           what, first_iter, max_staging_bytes)
+
     def curves_pick(self, draws=None, n=100, seed=None, first_iter=None) -> dict:
         """:func:`fitoct_amd.genquant.generated_quantities` without the download: dict(index,
         theta, yGP, dL, m, resid, br) of ``n`` post-warmup draws chosen at random (``seed``) or
@@ -706,6 +874,14 @@ class Batch(_LastRun):
         """Posterior bands of the last run (:meth:`Plan.curves`) of every file in one call: a
         list with one dict per problem, or problem ``problem``'s dict."""
         return self._curves(problem, what, probs, first_iter, max_staging_bytes)
+
+    def pairs(self, problem=None, pars=None, n_bins: int = 32, planes: int = 1,
+              range_probs=(0, 1), ranges=None, log=(), what=PAIRS_WHAT, first_iter=None,
+              max_staging_bytes: int = 0):
+        """The pairs plot of the last run (:meth:`Plan.pairs`) of every file in one call: a
+        list with one dict per problem, or problem ``problem``'s dict."""
+        return self._pairs(problem, self.cfg.chains, pars, n_bins, planes, range_probs, ranges,
+                           log, what, first_iter, max_staging_bytes)
 
     def curves_pick(self, problem: int, draws=None, n=100, seed=None, first_iter=None) -> dict:
         """:meth:`Plan.curves_pick` for problem ``problem`` of the last run."""

@@ -44,7 +44,7 @@ SOURCES = [
     ("nuts_lasso", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=1"]),
     ("nuts_horseshoe", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=2"]),
     ("nuts_monoexp", "nuts_device.hip", "hipcc", _KERNEL + ["-DFITOCT_FAMILY=3"]),
-    # what the three posterior tables below share: its kernels, compiled once (no family parameter)
+    # what the four posterior tables below share: its kernels, compiled once (no family parameter)
     ("posterior_common", "posterior_common.hip", "hipcc", _KERNEL),
     # the posterior summary's entry points
     ("summary_device", "summary_device.hip", "hipcc", _KERNEL),
@@ -52,6 +52,8 @@ SOURCES = [
     ("monitor_device", "monitor_device.hip", "hipcc", _KERNEL),
     # the posterior curves' kernels and entry points
     ("curves_device", "curves_device.hip", "hipcc", _KERNEL),
+    # the pairs plot's kernels (digitise, marginals, panels, correlation) and entry points
+    ("pairs_device", "pairs_device.hip", "hipcc", _KERNEL),
     ("fitoct_api", "fitoct_api.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("multi_device", "multi_device.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("host_model", "host_model.cpp", "g++", ["-O2", "-std=c++17"]),
@@ -62,7 +64,8 @@ SOURCES = [
 ]
 # objects whose kernels' resource remarks are kept beside them (<object>.resources.txt)
 RECORDED = [n for n, *_ in SOURCES if n.startswith("nuts_")] + ["posterior_common", "summary_device",
-                                                                         "monitor_device", "curves_device"]
+                                                                         "monitor_device", "curves_device",
+                                                                         "pairs_device"]
 # FITOCT_PROFILE=1: a diagnostic build whose kernels record cycle stamps
 # (read with FITOCT_STAMPS=1); production builds carry no timing code.
 PROFILE = os.environ.get("FITOCT_PROFILE", "0") not in ("", "0")

@@ -92,10 +92,12 @@ struct RowBlock {
 };
 // The workgroup's rows, contiguous in `draws`, read coalesced into tile[r * Wp + col],
 // Wp = k.W | 1 (odd: rows land on different banks); ends with the barrier.
-__device__ inline RowBlock load_row_tile(const KShape& k, const double* draws, double* tile) {
+// b: the row block, in 0 .. row_blocks(k.n) * k.C * k.G; a workgroup that loops over row blocks
+// puts a barrier between its last read of the tile and the next load.
+__device__ inline RowBlock load_row_tile(const KShape& k, const double* draws, double* tile,
+                                         int64_t b) {
   const int Wp = k.W | 1;
   const int rblocks = row_blocks(k.n);
-  int64_t b = blockIdx.x;
   const int rb = (int)(b % rblocks);
   b /= rblocks;
   const int c = (int)(b % k.C), g = (int)(b / k.C);
@@ -107,6 +109,9 @@ __device__ inline RowBlock load_row_tile(const KShape& k, const double* draws, d
   }
   __syncthreads();
   return RowBlock{g, c, i0, rows};
+}
+__device__ inline RowBlock load_row_tile(const KShape& k, const double* draws, double* tile) {
+  return load_row_tile(k, draws, tile, (int64_t)blockIdx.x);
 }
 
 // ---- device buffers -------------------------------------------------------------------------

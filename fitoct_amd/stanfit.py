@@ -196,6 +196,18 @@ class StanFit:
         prob, raw = self._source[1], self._source[3]
         return monitor_rows(monitor_host(raw, prob, self.warmup)[0], prob, pars)
 
+    def pairs(self, pars=None, n_bins=32, planes=1, range_probs=(0, 1), ranges=None, log=(),
+              what=None):
+        """The pairs plot of the post-warmup draws on the host (``fitoct_pairs_host``): the dict
+        of :meth:`fitoct_amd.api.Plan.pairs`.  Needs the raw draws of a sampled fit
+        (:meth:`from_output`)."""
+        if self._source is None or self._source[0] != "sample":
+            raise ValueError("pairs() needs a sampled fit built by StanFit.from_output")
+        from .api import PAIRS_WHAT, pairs_host, pairs_rows
+        prob, raw = self._source[1], self._source[3]
+        return pairs_rows(pairs_host(raw, prob, self.warmup, pars, n_bins, planes, range_probs,
+                                     ranges, log, PAIRS_WHAT if what is None else what))
+
     def print(self, pars=None, digits=3):
         s = self.summary(pars)
         if not s:

@@ -648,6 +648,93 @@ int32_t fitoct_batch_curves_pick_params(fitoct_batch* batch, int32_t group,
                                         const fitoct_summary_config* cfg, int32_t n_pick,
                                         const int64_t* pick, double* theta, double* ygp);
 
+/* ---- pairs plot (added within ABI 8: new entries only, no struct above changed) -------------- *
+ * What pairs(fit, pars = pars, gap = 0) (plotExpGP.R:47), rgumlib::SAPlot (plotExpGP.R:49),
+ * FitOCTLib::plotPriPostAll (priPost.R:22) and stan_hist (Tests/testGamma.R:50) reduce the draws
+ * to, from draws that stay in HBM: per selected column the marginal histogram, per couple of
+ * columns (a *panel*) the joint histogram, and the correlation matrix, over the
+ * S = chains (iters_saved - first_iter) post-warmup draws pooled over chains
+ * (draw s = chain n + iteration).
+ * cols[0 .. n_cols): distinct OUTPUT-layout columns (rows of the summary table, 0 .. P - 1), in
+ * any order; that order is the order of every output.  Column values are the summary's.
+ * Range of column j of group g: ranges[g][j] = (lo, hi) where both are finite; otherwise (a NaN
+ * entry, or ranges NULL) the type-7 quantiles of the pooled values at range_probs = (p_lo, p_hi),
+ * by the summary's select and interpolation: lo and hi are, bit for bit, what the
+ * fitoct_summary_* entry of the same route returns for those probabilities ((0, 1): the minimum
+ * and the maximum).
+ * Edges e_0 .. e_nb (nb = n_bins): e_0 = lo and e_nb = hi exactly; between them
+ * e_k = lo + (hi - lo) (k / nb), or for a column whose bit is set in log_mask (bit j: cols[j])
+ * e_k = lo exp(log(hi / lo) k / nb).  One host function builds them for both routes.
+ * A column has no grid -- its edges are NaN and its counts 0 in `hist1`, `outside` and every
+ * panel it belongs to, for that group only -- when it holds a NaN, lo or hi is not finite,
+ * lo >= hi, it is a log column with lo <= 0, or its edges are not strictly increasing (lasso's
+ * constant `lambda`).
+ * Bin k holds e_k <= v < e_k+1, the last bin is closed (e_nb-1 <= v <= e_nb): numpy's rule for
+ * explicit edges, decided by comparisons against the edge array only, so the counts are exact
+ * and the same on the host, on the device and in numpy.  Values below lo or above hi fall in no
+ * bin and are counted in `outside`.
+ * Planes: plane 0 counts every draw; plane 1 (planes = 2) the draws whose raw divergent__ is not
+ * 0 (rstan's pairs marks them in red).
+ * Outputs, each NULL if not wanted (at least one must be given):
+ *   edges   [n_groups][n_cols][nb + 1]
+ *   hist1   [n_groups][n_cols][planes][nb]           marginal counts
+ *   outside [n_groups][n_cols][2]                    draws below lo, above hi (all draws)
+ *   hist2   [n_groups][n_panels][planes][nb][nb]     panel (a, b), a < b in selection order,
+ *           lexicographic (n_panels = n_cols (n_cols - 1) / 2): cell [ka][kb] counts the draws
+ *           in bin ka of column a and bin kb of column b.  With range_probs (0, 1) the row and
+ *           column sums of a panel are the two marginals
+ *   corr    [n_groups][n_cols][n_cols]  Pearson's correlation over all S draws (no range
+ *           restriction), in two passes: the pooled means, then the centred cross-products.
+ *           The diagonal is exactly 1, the matrix symmetric bit for bit; every entry that
+ *           involves a column with a NaN or with zero variance is NaN
+ * The device route keeps one byte per (column, draw), the bin, and one per draw, the divergent
+ * flag: (n_cols + 1) S bytes per group (65 MB at 64 columns x 1 M draws), which lie outside
+ * max_staging_bytes; that cap holds the columns staged for the automatic ranges (skipped when
+ * every range is given).  The cross-product sums are partitioned by the shape alone and added
+ * in a fixed order, and the counts are integers: results are the same bit for bit from call to
+ * call, for any max_staging_bytes, and on any device.
+ * Refusals, all before the first HIP call (FITOCT_E_ARG): the summary's shape refusals, and
+ * n_cols outside 1..64, a column outside 0..P-1 or repeated, n_bins outside 2..64, planes not 1
+ * or 2, not 0 <= p_lo < p_hi <= 1, a log_mask bit at or above n_cols, every output NULL. */
+typedef struct fitoct_pairs_config {
+  int32_t  first_iter;          /* leading saved iterations to skip (the saved warmup) */
+  int32_t  n_cols;              /* 1..64; default 0: the caller chooses */
+  int32_t  cols[64];            /* OUTPUT-layout column indices, distinct */
+  int32_t  n_bins;              /* 2..64; default 32 */
+  int32_t  planes;              /* 1, or 2: a second count plane of the divergent draws */
+  double   range_probs[2];      /* automatic ranges; default (0, 1) */
+  uint64_t log_mask;            /* bit j: geometric edges for cols[j] */
+  int64_t  max_staging_bytes;   /* as fitoct_summary_config */
+  int32_t  device;              /* ordinal of the device d_draws lives on */
+} fitoct_pairs_config;
+typedef struct fitoct_pairs_out {
+  double*  edges;
+  int64_t* hist1;
+  int64_t* outside;
+  int64_t* hist2;
+  double*  corr;
+} fitoct_pairs_out;
+void fitoct_default_pairs_config(fitoct_pairs_config* cfg);
+/* element counts of edges, hist1, outside, hist2, corr for n_groups groups */
+int32_t fitoct_pairs_sizes(const fitoct_pairs_config* cfg, int32_t n_groups, int64_t sizes[5]);
+/* ranges: [n_groups][n_cols][2] or NULL.  fitoct_pairs_device runs on `stream` (NULL = default
+ * stream) and synchronises it before returning; draws as for fitoct_summary_device. */
+int32_t fitoct_pairs_device(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                            int32_t iters_saved, const void* d_draws, const double* ranges,
+                            const fitoct_pairs_config* cfg, void* stream,
+                            const fitoct_pairs_out* out);
+/* the same computation on the host (draws: a host buffer; cfg->device and max_staging_bytes
+ * are ignored): the reference the device route is tested against */
+int32_t fitoct_pairs_host(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
+                          int32_t iters_saved, const double* draws, const double* ranges,
+                          const fitoct_pairs_config* cfg, const fitoct_pairs_out* out);
+/* The table of the last completed run's draws where they lie; refused exactly where
+ * fitoct_plan_summary / fitoct_batch_summary are (cfg->device is ignored). */
+int32_t fitoct_plan_pairs(fitoct_plan* plan, const double* ranges, const fitoct_pairs_config* cfg,
+                          const fitoct_pairs_out* out);
+int32_t fitoct_batch_pairs(fitoct_batch* batch, const double* ranges,
+                           const fitoct_pairs_config* cfg, const fitoct_pairs_out* out);
+
 #ifdef __cplusplus
 }
 #endif
