@@ -103,6 +103,25 @@ struct Chain {
         LV(L.lvls(slot_)), RNG(L.lvls(slot_) + (size_t)P_.max_depth * NLVL * VLEN), MP(L.mp(slot_)),
         part(L.part()), Kinv(L.kinv()), bv(L.bv()),
         lane(lane_), slot(slot_), lc(lc_), nct(nct_) {
+    // The chain area's base lives in ONE VGPR for the life of the chain, and the vectors, sums,
+    // AUX and levels are constant offsets from it.  As wave-uniform SGPR values the compiler
+    // copied the base into a VGPR in front of nearly every ds_ access to a chain scalar
+    // (v_mov_b32 from the SGPR: 372 static copies in the headline kernel, 134 now), and kept
+    // the four sub-bases in SGPRs of their own, spilled to VGPR lanes and reloaded per action.
+    // Opaque to the compiler from here on (it may not treat the value as uniform again); the
+    // alignment it could derive from the carve is stated instead, so that the 16-byte LDS reads
+    // of AUX / SUMS stay single instructions.  Addresses only: no value changes.
+    static_assert(sizeof(ChainScalars) % 16 == 0 && (NVEC * VLEN * 8) % 16 == 0 &&
+                      (NSLOT * 8) % 16 == 0 && (NAUX * 8) % 16 == 0 &&
+                      Lds<PPL>::head_bytes(1) % 16 == 0 && Lds<PPL>::head_bytes(2) % 16 == 0 &&
+                      Lds<PPL>::chain_bytes(1) % 16 == 0 && Lds<PPL>::chain_bytes(2) % 16 == 0,
+                  "chain areas are 16-byte aligned");
+    asm volatile("" : "+v"(Sp));
+    __builtin_assume(((uint32_t)(uintptr_t)Sp & 15u) == 0);
+    Vb = (AS_LDS double*)((AS_LDS char*)Sp + sizeof(ChainScalars));
+    SUMS = Vb + NVEC * VLEN;
+    AUX = SUMS + NSLOT;
+    LV = AUX + NAUX;
     gid = Pr().chain_offset + lc;
     pix = lc;
     // tiles of G <= 2 chains: NUTS wave G + c helps chain slot c (tile of one chain: wave 1)
@@ -576,6 +595,7 @@ struct Chain {
   // the uniforms leaf j of the subtree of depth d will consume in its merges (and the
   // top-level merge's, for the subtree's last leaf)
   __device__ void tree_uniforms(const int d, const int j, const uint32_t t) const {
+    FITOCT_MARK(tree_uniforms);   // (what follows the inlined prior_part)
     {
       // Leaf j completes the merges of levels l < nm (trailing ones of j).
       // The k-th level-l merge of a subtree sits at leaf (k + 1) 2^(l+1) - 1; each
@@ -608,6 +628,7 @@ struct Chain {
       // the leaf's position, momentum and the metric are read while the bin sums reduce
       const V q = ld(V_CUR_Q), p = ld(V_CUR_P), minv = ld(V_MINV);
       const double lp = finish_grad(g, s0);
+      FITOCT_MARK(act_grad_store);   // (what follows the inlined finish_grad)
       sub(4, ts);
       st(V_CUR_G, g);
       Sp->cur_lp = lp;
@@ -754,6 +775,7 @@ struct Chain {
     st(V_CUR_P, p);
     st(V_CUR_Q, q);
     write_mp(q);
+    FITOCT_MARK(leapfrog_staged);   // (what follows the inlined write_mp is the caller's)
     return A_YIELD;
   }
   __device__ int act_write_mp() {
@@ -925,6 +947,7 @@ struct Chain {
   // same values as the plain path: draws are bitwise identical.
   __device__ int leaf_spec(const V& q, const V& p, const V& g, const V& minv, const double cur_lp,
                            const double cur_s2) {
+    FITOCT_MARK(leaf_spec);
     const double e = Sp->lf_e;
     const int d = uni(Sp->depth), j = uni(Sp->leaf);
     const bool last = j == (1 << d) - 1;
@@ -953,6 +976,7 @@ struct Chain {
       en = dirn ? Sp->eps_used : -Sp->eps_used;
     }
     leapfrog_stage(qs, ps, gs, minv, en);
+    FITOCT_MARK(leaf_spec_park);
     if (deep) {   // hand leaf k to the booking helper (deep_book)
 #pragma unroll
       for (int s = 0; s < PPL; ++s) {
@@ -986,6 +1010,7 @@ struct Chain {
     const int r = KLDS ? leaf_book_split(ld(V_PG), ld(V_CUR_G), ld(V_CA), ld(V_MINV), Sp->cur_lp,
                                          Sp->cur_s2)
                        : leaf_book_split(k_q, k_pe, k_g, ld(V_MINV), Sp->cur_lp, Sp->cur_s2);
+    FITOCT_MARK(act_spec_book_next);   // (what follows the inlined leaf_book_split)
     if (r == LB_NEXT) {   // the rest of act_begin_subtree (the top merge set depth d + 1)
       // the next subtree grows from trajectory end k_dirn: the far end if the direction
       // changed (untouched by the top merge), else the end the top merge just set to this

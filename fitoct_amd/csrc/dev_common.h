@@ -132,12 +132,20 @@ constexpr unsigned long long LEAF_WAIT_TICKS = 30ULL * TICKS_PER_S;
 // sweep, a profiler or a deep tree never fails a healthy chain with ERR_TIMEOUT, and a
 // fault still ends the launch.  expired(T) is true once T ticks passed since poll SPIN_LIMIT.
 struct Patience {
-  long long n = 0;
+  // polls so far, held at SPIN_LIMIT + 1 once the clock is read: 32 bits, so that a poll's
+  // count and compare are scalar instructions (a 64-bit ordered compare is a VALU one)
+  uint32_t n = 0;
   unsigned long long t0 = 0;
   __device__ __forceinline__ bool expired(unsigned long long ticks) {
-    if (++n <= SPIN_LIMIT) return false;
+    if (n < (uint32_t)SPIN_LIMIT) {
+      ++n;
+      return false;
+    }
     const unsigned long long t = __builtin_amdgcn_s_memrealtime();
-    if (n == SPIN_LIMIT + 1) t0 = t;
+    if (n == (uint32_t)SPIN_LIMIT) {
+      t0 = t;
+      n = (uint32_t)SPIN_LIMIT + 1;
+    }
     __builtin_amdgcn_s_sleep(32);
     return t - t0 > ticks;
   }

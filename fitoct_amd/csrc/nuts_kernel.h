@@ -16,6 +16,21 @@
 // only there, after tile_migrate.h (sweep_math.h needs the opposite regime and says why).
 #pragma once
 
+// A NUTS wave's wait for its chain's sweeps: grad_cnt[c] reaching `want`.  The counter's
+// address stays in one VGPR for the whole wait and the polled value goes through
+// v_readfirstlane, so a poll is one LDS read, one lane read and scalar compares: no reload of
+// a spilled address and no lane-mask loop around a wave-uniform count.  False: the wait expired.
+__device__ __forceinline__ bool wait_sweeps(const int* cnt, const int want, Patience& w) {
+  const AS_LDS int* p = (const AS_LDS int*)cnt;
+  asm volatile("" : "+v"(p));
+  const int n = __builtin_amdgcn_readfirstlane(want);   // (the slot's epoch is wave-uniform)
+  while (__builtin_amdgcn_readfirstlane(__atomic_load_n(p, __ATOMIC_RELAXED)) < n) {
+    if (w.expired(LEAF_WAIT_TICKS)) return false;
+    __builtin_amdgcn_s_sleep(1);
+  }
+  return true;
+}
+
 // Dataflow pipeline inside a tile.  The NUTS wave of chain c writes the next
 // position's parameters to MP[c] and enqueues c in an LDS ring (64-bit entries
 // {sequence number, chain}); the gradient waves drain the ring in order, each
@@ -985,17 +1000,10 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
           continue;
         }
         if (spec && (y == Ch::A_SPEC_WAIT || y == Ch::A_SPEC_DISCARD)) {
-          bool late = false;
           Patience w;
           const long long w0 = stamp ? (long long)__builtin_amdgcn_s_memtime() : 0;
           if (stamp) t_busy += w0 - s0;
-          while (lds_load(&grad_cnt[c]) < (int)(NGW * epoch)) {
-            if (w.expired(LEAF_WAIT_TICKS)) {
-              late = true;
-              break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-          }
+          const bool late = !wait_sweeps(&grad_cnt[c], (int)(NGW * epoch), w);
           wave_fence();   // nothing of the next action is read before the sweep and the helper are done
           if (stamp) {
             const long long t1 = (long long)__builtin_amdgcn_s_memtime();
@@ -1027,22 +1035,10 @@ __global__ void __launch_bounds__(TPB, 2) nuts_kernel(const KParams* __restrict_
           // rarely, so the waiting wave leaves the SIMD's issue to the gradient wave.
           if (P.G >= 2 && (BPT >= 8 || BPT == 0)) {
             __builtin_amdgcn_s_setprio(0);
-            while (lds_load(&grad_cnt[c]) < (int)(NGW * epoch)) {
-              if (w.expired(LEAF_WAIT_TICKS)) {
-                late = true;
-                break;
-              }
-              __builtin_amdgcn_s_sleep(1);
-            }
+            late = !wait_sweeps(&grad_cnt[c], (int)(NGW * epoch), w);
             __builtin_amdgcn_s_setprio(3);
           } else {
-            while (lds_load(&grad_cnt[c]) < (int)(NGW * epoch)) {
-              if (w.expired(LEAF_WAIT_TICKS)) {
-                late = true;
-                break;
-              }
-              __builtin_amdgcn_s_sleep(1);
-            }
+            late = !wait_sweeps(&grad_cnt[c], (int)(NGW * epoch), w);
           }
           if (stamp) {
             const long long t1 = (long long)__builtin_amdgcn_s_memtime();
