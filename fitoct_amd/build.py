@@ -55,11 +55,13 @@ SOURCES = [
     # the pairs plot's kernels (digitise, marginals, panels, correlation) and entry points
     ("pairs_device", "pairs_device.hip", "hipcc", _KERNEL),
     ("fitoct_api", "fitoct_api.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
+    ("batch", "batch.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("multi_device", "multi_device.cpp", "hipcc", [f"--offload-arch={ARCH}", "-O2", "-std=c++17"]),
     ("host_model", "host_model.cpp", "g++", ["-O2", "-std=c++17"]),
     ("optimize", "optimize.cpp", "g++", ["-O2", "-std=c++17"]),
     ("stan_output", "stan_output.cpp", "g++", ["-O2", "-std=c++17"]),
     ("schedule", "schedule.cpp", "g++", ["-O2", "-std=c++17"]),
+    ("plan_data", "plan_data.cpp", "g++", ["-O2", "-std=c++17"]),
     ("stamps_report", "stamps_report.cpp", "g++", ["-O2", "-std=c++17"]),
 ]
 # objects whose kernels' resource remarks are kept beside them (<object>.resources.txt)

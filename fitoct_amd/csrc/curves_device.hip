@@ -414,31 +414,36 @@ int curves_pick_checked(const fitoct_problem* probs, int n_groups, int chains, i
                      br, theta, ygp);
 }
 
-// ---- the last run of a plan or a batch (plan_where / batch_where: the refusals) --------------
-int batch_pick(fitoct_batch* b, int group, const fitoct_summary_config* cfg, int n_pick,
-               const int64_t* pick, double* dL, double* m, double* resid, double* br,
-               double* theta, double* ygp) {
-  if (!b || !cfg) return fail(FITOCT_E_ARG, "curves pick: NULL argument");
-  Where w;
-  FITOCT_TRY(batch_where(b, "the curves need", w));
-  if (group < 0 || group >= (int)w.probs.size())
-    return fail(FITOCT_E_ARG, "curves pick: group out of range");
-  fitoct_summary_config c = *cfg;
-  c.device = w.device;
-  return curves_pick_checked(&w.probs[group], 1, w.chains, w.iters_saved,
-                             w.draws + (size_t)group * w.group_bytes, &c, nullptr, n_pick, pick, dL,
-                             m, resid, br, theta, ygp);
+// ---- the last run of a plan or a batch (on_last_run: the refusals) ---------------------------
+// the picked draws of a plan's run, or of group `group` of a batch's
+template <class Handle>
+int last_run_pick(const char* fn, Handle* h, int group, const fitoct_summary_config* cfg,
+                  int n_pick, const int64_t* pick, double* dL, double* m, double* resid,
+                  double* br, double* theta, double* ygp) {
+  return guarded(fn, [&]() -> int32_t {
+    return on_last_run(h, "curves pick", "the curves need", cfg, true,
+                       [&](const Where& w, const fitoct_summary_config& c) {
+                         if (group < 0 || group >= (int)w.probs.size())
+                           return fail(FITOCT_E_ARG, "curves pick: group out of range");
+                         return curves_pick_checked(
+                             &w.probs[group], 1, w.chains, w.iters_saved,
+                             w.draws + (size_t)group * w.group_bytes, &c, nullptr, n_pick, pick,
+                             dL, m, resid, br, theta, ygp);
+                       });
+  });
 }
 
-int plan_pick(fitoct_plan* pl, const fitoct_summary_config* cfg, int n_pick, const int64_t* pick,
-              double* dL, double* m, double* resid, double* br, double* theta, double* ygp) {
-  if (!pl || !cfg) return fail(FITOCT_E_ARG, "curves pick: NULL argument");
-  Where w;
-  FITOCT_TRY(plan_where(pl, "the curves need", w));
-  fitoct_summary_config c = *cfg;
-  c.device = w.device;
-  return curves_pick_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, &c, nullptr,
-                             n_pick, pick, dL, m, resid, br, theta, ygp);
+template <class Handle>
+int last_run_curves(const char* fn, Handle* h, int what, const fitoct_summary_config* cfg,
+                    double* out) {
+  return guarded(fn, [&]() -> int32_t {
+    return on_last_run(h, "curves", "the curves need", cfg, out != nullptr,
+                       [&](const Where& w, const fitoct_summary_config& c) {
+                         return curves_device_checked(w.probs.data(), (int32_t)w.probs.size(),
+                                                      w.chains, w.iters_saved, w.draws, what, &c,
+                                                      nullptr, out);
+                       });
+  });
 }
 
 }  // namespace
@@ -476,28 +481,12 @@ int32_t fitoct_curves_device(const fitoct_problem* probs, int32_t n_groups, int3
 
 int32_t fitoct_plan_curves(fitoct_plan* pl, int32_t what, const fitoct_summary_config* cfg,
                            double* out) {
-  return guarded(__func__, [&]() -> int32_t {
-    if (!pl || !cfg || !out) return fail(FITOCT_E_ARG, "curves: NULL argument");
-    Where w;
-    FITOCT_TRY(plan_where(pl, "the curves need", w));
-    fitoct_summary_config c = *cfg;
-    c.device = w.device;
-    return curves_device_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, what, &c,
-                                 nullptr, out);
-  });
+  return last_run_curves(__func__, pl, what, cfg, out);
 }
 
 int32_t fitoct_batch_curves(fitoct_batch* b, int32_t what, const fitoct_summary_config* cfg,
                             double* out) {
-  return guarded(__func__, [&]() -> int32_t {
-    if (!b || !cfg || !out) return fail(FITOCT_E_ARG, "curves: NULL argument");
-    Where w;
-    FITOCT_TRY(batch_where(b, "the curves need", w));
-    fitoct_summary_config c = *cfg;
-    c.device = w.device;
-    return curves_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains, w.iters_saved,
-                                 w.draws, what, &c, nullptr, out);
-  });
+  return last_run_curves(__func__, b, what, cfg, out);
 }
 
 int32_t fitoct_curves_pick_device(const fitoct_problem* probs, int32_t n_groups, int32_t chains,
@@ -514,33 +503,27 @@ int32_t fitoct_curves_pick_device(const fitoct_problem* probs, int32_t n_groups,
 int32_t fitoct_plan_curves_pick(fitoct_plan* pl, const fitoct_summary_config* cfg, int32_t n_pick,
                                 const int64_t* pick, double* dL, double* m, double* resid,
                                 double* br) {
-  return guarded(__func__, [&]() -> int32_t {
-    return plan_pick(pl, cfg, n_pick, pick, dL, m, resid, br, nullptr, nullptr);
-  });
+  return last_run_pick(__func__, pl, 0, cfg, n_pick, pick, dL, m, resid, br, nullptr, nullptr);
 }
 
 int32_t fitoct_batch_curves_pick(fitoct_batch* b, int32_t group, const fitoct_summary_config* cfg,
                                  int32_t n_pick, const int64_t* pick, double* dL, double* m,
                                  double* resid, double* br) {
-  return guarded(__func__, [&]() -> int32_t {
-    return batch_pick(b, group, cfg, n_pick, pick, dL, m, resid, br, nullptr, nullptr);
-  });
+  return last_run_pick(__func__, b, group, cfg, n_pick, pick, dL, m, resid, br, nullptr, nullptr);
 }
 
 int32_t fitoct_plan_curves_pick_params(fitoct_plan* pl, const fitoct_summary_config* cfg,
                                        int32_t n_pick, const int64_t* pick, double* theta,
                                        double* ygp) {
-  return guarded(__func__, [&]() -> int32_t {
-    return plan_pick(pl, cfg, n_pick, pick, nullptr, nullptr, nullptr, nullptr, theta, ygp);
-  });
+  return last_run_pick(__func__, pl, 0, cfg, n_pick, pick, nullptr, nullptr, nullptr, nullptr,
+                       theta, ygp);
 }
 
 int32_t fitoct_batch_curves_pick_params(fitoct_batch* b, int32_t group,
                                         const fitoct_summary_config* cfg, int32_t n_pick,
                                         const int64_t* pick, double* theta, double* ygp) {
-  return guarded(__func__, [&]() -> int32_t {
-    return batch_pick(b, group, cfg, n_pick, pick, nullptr, nullptr, nullptr, nullptr, theta, ygp);
-  });
+  return last_run_pick(__func__, b, group, cfg, n_pick, pick, nullptr, nullptr, nullptr, nullptr,
+                       theta, ygp);
 }
 
 }  // extern "C"

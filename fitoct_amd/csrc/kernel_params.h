@@ -1,4 +1,4 @@
-// Launch parameters shared by the host planner (fitoct_api.cpp) and the device
+// Launch parameters shared by the host planner (plan_data.cpp, fitoct_api.cpp) and the device
 // sampler (nuts_device.hip).  Plain data, passed by value as a kernel argument.
 #pragma once
 #include <stdint.h>

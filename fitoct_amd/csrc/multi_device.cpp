@@ -66,17 +66,7 @@ int buffer_device(const void* p, int& dev) {
 
 namespace {
 
-// The calling thread's HIP device is restored when a multi-device call returns (the
-// shards switch it; a caller such as PyTorch keeps its own notion of the current device).
-struct DeviceRestore {
-  int dev = -1;
-  DeviceRestore() {
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  }
-  ~DeviceRestore() {
-    if (dev >= 0) (void)hipSetDevice(dev);
-  }
-};
+// (the calling thread's HIP device is put back when a multi-device call returns: DeviceKeep)
 
 // f(r) for r in [0, n) on one host thread per device (r = 0 on the calling thread).
 // Returns FITOCT_OK, or the status of the lowest-numbered failure that is not a
@@ -122,10 +112,9 @@ bool in_place(const void* d_draws, int dev, int gdev) {
 // a non-blocking stream on `dev` for one shard: the shards of a group never order
 // against each other, nor against the synchronous status reads / peer copies issued
 // for another shard, through the device's default stream
-int own_stream(int dev, hipStream_t& st) {
+int own_stream(int dev, Stream& st) {
   HIP_TRY(hipSetDevice(dev));
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  return FITOCT_OK;
+  return st.create(hipStreamNonBlocking);
 }
 
 // Peer access between the gather buffer's device and a shard's device, enabled once per
@@ -158,23 +147,15 @@ int enable_peer(int gdev, int sdev) {
 // recorded on the buffer device's NULL stream, which every in-place shard's private stream
 // waits on before its first write into the buffer.
 struct NullStreamFence {
-  hipEvent_t ev = nullptr;
-  int dev = -1;
-  ~NullStreamFence() {
-    if (ev) {
-      (void)hipSetDevice(dev);
-      (void)hipEventDestroy(ev);
-    }
-  }
+  Event ev;
   int record(int gdev) {
-    dev = gdev;
     HIP_TRY(hipSetDevice(gdev));
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(ev, nullptr));
+    FITOCT_TRY(ev.create(hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(ev.p, nullptr));
     return FITOCT_OK;
   }
   int order(hipStream_t st) const {
-    if (ev) HIP_TRY(hipStreamWaitEvent(st, ev, 0));
+    if (ev.p) HIP_TRY(hipStreamWaitEvent(st, ev.p, 0));
     return FITOCT_OK;
   }
 };
@@ -189,12 +170,11 @@ size_t chain_bytes(const fitoct_plan* sh) {
 int group_plan_create(const fitoct_problem* prob, const fitoct_config* cfg,
                       const std::vector<int>& devs, fitoct_plan** out) {
   const int n = (int)devs.size(), C = cfg->chains;
-  std::unique_ptr<fitoct_plan, void (*)(fitoct_plan*)> guard(new fitoct_plan(),
-                                                             fitoct_plan_destroy);
+  std::unique_ptr<fitoct_plan> guard(new fitoct_plan());
   fitoct_plan* pl = guard.get();
   pl->shards.assign(n, nullptr);
   pl->shard_off.assign(n, 0);
-  DeviceRestore keep;
+  DeviceKeep keep;
   const int rc = on_devices(n, [&](int r) -> int {
     int off, cnt;
     block_range(C, n, r, off, cnt);
@@ -242,7 +222,7 @@ int group_plan_set_init(fitoct_plan* pl, const double* q, const double* eps, con
   // whole plan as it was (no half warm-started plan)
   const int ck = check_init(pl->kp.chains, D, q, eps, minv);
   if (ck) return ck;
-  DeviceRestore keep;
+  DeviceKeep keep;
   for (size_t r = 0; r < pl->shards.size(); ++r) {
     const size_t o = (size_t)pl->shard_off[r];
     const int rc = fitoct_plan_set_init(pl->shards[r], q ? q + o * D : nullptr,
@@ -263,7 +243,7 @@ int group_plan_launch(fitoct_plan* pl, void* d_draws, void* stream) {
     const int rc = buffer_device(d_draws, gdev);
     if (rc) return rc;
   }
-  DeviceRestore keep;
+  DeviceKeep keep;
   NullStreamFence fence;
   if (d_draws) {
     bool any_direct = false;
@@ -285,9 +265,9 @@ int group_plan_launch(fitoct_plan* pl, void* d_draws, void* stream) {
     const bool direct = in_place(d_draws, sh->cfg.device, gdev);
     void* dst = direct ? (char*)d_draws + chain_bytes(sh) * (size_t)pl->shard_off[r] : nullptr;
     int rc = FITOCT_OK;
-    if (!sh->own_stream) rc = own_stream(sh->cfg.device, sh->own_stream);
-    if (!rc && direct) rc = fence.order(sh->own_stream);
-    if (!rc) rc = fitoct_plan_launch(sh, dst, sh->own_stream);
+    if (!sh->own_stream.p) rc = own_stream(sh->cfg.device, sh->own_stream);
+    if (!rc && direct) rc = fence.order(sh->own_stream.p);
+    if (!rc) rc = fitoct_plan_launch(sh, dst, sh->own_stream.p);
     if (rc) {   // stop what was launched before reporting
       const std::string msg = g_last_error;
       for (size_t k = 0; k < r; ++k) {
@@ -307,7 +287,7 @@ int group_plan_launch(fitoct_plan* pl, void* d_draws, void* stream) {
 int group_plan_poll(fitoct_plan* pl, int64_t* done, int64_t* total, int32_t* finished) {
   int64_t d = 0, t = 0;
   int32_t f = 1;
-  DeviceRestore keep;
+  DeviceKeep keep;
   for (fitoct_plan* sh : pl->shards) {
     int64_t ds = 0, ts = 0;
     int32_t fs = 0;
@@ -339,7 +319,7 @@ int group_plan_wait(fitoct_plan* pl) {
     for (int k = 0; k < n; ++k)
       if (k != r) (void)fitoct_plan_cancel(pl->shards[k]);
   };
-  DeviceRestore keep;
+  DeviceKeep keep;
   // every error return of a device's part (its wait, the status read, the peer copy of its
   // block) cancels the other devices: "a failure on one device cancels the others"
   auto part = [&](int r) -> int {
@@ -381,7 +361,7 @@ int group_plan_download(fitoct_plan* pl, fitoct_result* res) {
   if (res->draws && res->draws_capacity < (int64_t)k.chains * per_chain)
     return fail(FITOCT_E_ARG, "draws buffer too small");
   std::vector<fitoct_result> sub(n);
-  DeviceRestore keep;
+  DeviceKeep keep;
   const int rc = on_devices(n, [&](int r) -> int {
     const size_t o = (size_t)pl->shard_off[r];
     fitoct_plan* sh = pl->shards[r];
@@ -429,14 +409,13 @@ int group_sample(const fitoct_problem* prob, const fitoct_config* cfg,
 int group_batch_create(const fitoct_problem* probs, int n_problems, const fitoct_config* cfg,
                        const std::vector<int>& devs, fitoct_batch** out) {
   const int n = (int)devs.size(), C = cfg->chains;
-  std::unique_ptr<fitoct_batch, void (*)(fitoct_batch*)> guard(new fitoct_batch(),
-                                                               fitoct_batch_destroy);
+  std::unique_ptr<fitoct_batch> guard(new fitoct_batch());
   fitoct_batch* b = guard.get();
   b->cfg = *cfg;
   b->n_problems = n_problems;
   b->subs.assign(n, nullptr);
   b->sub_off.assign(n, 0);
-  DeviceRestore keep;
+  DeviceKeep keep;
   const int rc = on_devices(n, [&](int r) -> int {
     int off, cnt;
     block_range(n_problems, n, r, off, cnt);
@@ -475,7 +454,7 @@ int group_batch_run(fitoct_batch* b, void* d_draws, void* stream) {
     if (rc) return rc;
   }
   const int n = (int)b->subs.size();
-  DeviceRestore keep;
+  DeviceKeep keep;
   NullStreamFence fence;
   if (d_draws) {
     bool any_direct = false;
@@ -491,36 +470,30 @@ int group_batch_run(fitoct_batch* b, void* d_draws, void* stream) {
   }
   // every flag is cleared before any device starts, so a cancellation raised by an early
   // failure is never undone by a later device's start
-  for (fitoct_batch* sb : b->subs) __atomic_store_n(sb->h_cancel, 0, __ATOMIC_SEQ_CST);
+  for (fitoct_batch* sb : b->subs) __atomic_store_n(sb->h_cancel.as<int>(), 0, __ATOMIC_SEQ_CST);
   auto cancel_others = [&](int r) {
     for (int k = 0; k < n; ++k)
-      if (k != r) __atomic_store_n(b->subs[k]->h_cancel, 1, __ATOMIC_SEQ_CST);
+      if (k != r) __atomic_store_n(b->subs[k]->h_cancel.as<int>(), 1, __ATOMIC_SEQ_CST);
   };
   // (every error return of a device's part cancels the other devices, the peer copy's too)
   auto part = [&](int r) -> int {
     fitoct_batch* sb = b->subs[r];
     char* slice = d_draws ? (char*)d_draws + b->per_bytes * (size_t)b->sub_off[r] : nullptr;
     const bool direct = in_place(d_draws, sb->cfg.device, gdev);
-    if (!sb->own_stream) {
-      const int e = own_stream(sb->cfg.device, sb->own_stream);
-      if (e) return e;
-    }
-    if (direct) {
-      const int e = fence.order(sb->own_stream);
-      if (e) return e;
-    }
+    if (!sb->own_stream.p) FITOCT_TRY(own_stream(sb->cfg.device, sb->own_stream));
+    if (direct) FITOCT_TRY(fence.order(sb->own_stream.p));
     // FITOCT_TEST_FAIL_ENTRY=r (tests only): device entry r fails before its launch, so
     // one GPU can exercise the cancellation of the other entries (read on every call)
     const char* inject = getenv("FITOCT_TEST_FAIL_ENTRY");
     const int e = (inject && atoi(inject) == r)
                       ? fail(FITOCT_E_INTERNAL, "injected failure (FITOCT_TEST_FAIL_ENTRY)")
-                      : batch_run_single(sb, direct ? slice : nullptr, sb->own_stream);
+                      : batch_run_single(sb, direct ? slice : nullptr, sb->own_stream.p);
     if (e) return e;   // the call fails: the other devices' chains stop at their next checked boundary
     // A failed chain of one file (non-finite init, step-size search) is that file's status
     // at download, as in a one-device batch: files are independent fits (FitOCT.R:70-124)
     // and the other files, on this device or another, run on.
     if (d_draws && !direct)
-      HIP_TRY(hipMemcpyPeer(slice, gdev, sb->d_draws, sb->cfg.device,
+      HIP_TRY(hipMemcpyPeer(slice, gdev, sb->d_draws.p, sb->cfg.device,
                             b->per_bytes * sb->plans.size()));
     return FITOCT_OK;
   };
@@ -541,7 +514,7 @@ int group_batch_download(fitoct_batch* b, int problem, fitoct_result* res) {
   if (!b->ran) return fail(FITOCT_E_ARG, "batch has not run");
   for (size_t r = b->subs.size(); r-- > 0;)
     if (problem >= b->sub_off[r]) {
-      DeviceRestore keep;
+      DeviceKeep keep;
       return fitoct_batch_download(b->subs[r], problem - b->sub_off[r], res);
     }
   return fail(FITOCT_E_INTERNAL, "problem not found in any sub-batch");

@@ -784,6 +784,18 @@ int pairs_device_checked(const fitoct_problem* probs, int n_groups, int chains, 
 
 using namespace fitoct;
 
+// the last run of a plan or of a batch (one body: on_last_run)
+template <class Handle>
+static int32_t last_run_pairs(const char* fn, Handle* h, const double* ranges, const fitoct_pairs_config* cfg, const fitoct_pairs_out* out) {
+  return guarded(fn, [&]() -> int32_t {
+    return on_last_run(h, "pairs", "the pairs plot needs", cfg, out != nullptr,
+                       [&](const Where& w, const fitoct_pairs_config& c) {
+                         return pairs_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains,
+                                                     w.iters_saved, w.draws, ranges, &c, nullptr, out);
+                       });
+  });
+}
+
 extern "C" {
 
 void fitoct_default_pairs_config(fitoct_pairs_config* cfg) {
@@ -828,28 +840,12 @@ int32_t fitoct_pairs_device(const fitoct_problem* probs, int32_t n_groups, int32
 
 int32_t fitoct_plan_pairs(fitoct_plan* pl, const double* ranges, const fitoct_pairs_config* cfg,
                           const fitoct_pairs_out* out) {
-  return guarded(__func__, [&]() -> int32_t {
-    if (!pl || !cfg || !out) return fail(FITOCT_E_ARG, "pairs: NULL argument");
-    Where w;
-    FITOCT_TRY(plan_where(pl, "the pairs plot needs", w));
-    fitoct_pairs_config c = *cfg;
-    c.device = w.device;
-    return pairs_device_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, ranges, &c,
-                                nullptr, out);
-  });
+  return last_run_pairs(__func__, pl, ranges, cfg, out);
 }
 
 int32_t fitoct_batch_pairs(fitoct_batch* b, const double* ranges, const fitoct_pairs_config* cfg,
                            const fitoct_pairs_out* out) {
-  return guarded(__func__, [&]() -> int32_t {
-    if (!b || !cfg || !out) return fail(FITOCT_E_ARG, "pairs: NULL argument");
-    Where w;
-    FITOCT_TRY(batch_where(b, "the pairs plot needs", w));
-    fitoct_pairs_config c = *cfg;
-    c.device = w.device;
-    return pairs_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains, w.iters_saved,
-                                w.draws, ranges, &c, nullptr, out);
-  });
+  return last_run_pairs(__func__, b, ranges, cfg, out);
 }
 
 }  // extern "C"

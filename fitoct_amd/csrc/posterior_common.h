@@ -31,12 +31,6 @@ constexpr int STAGE_ROWS = 32;          // rows of one chain per load_row_tile w
 constexpr int STAGE_THREADS = 256;
 constexpr int QT_MAX = 2 * MAX_PROBS;   // order statistics per column: x[lo], x[hi] per probability
 
-#define FITOCT_TRY(expr)          \
-  do {                            \
-    const int rc_ = (expr);       \
-    if (rc_) return rc_;          \
-  } while (0)
-
 // What a call computes: shapes checked by check_args.
 struct Shape {
   int G = 0, C = 0, I = 0, W = 0;   // groups, chains, saved iterations, raw columns
@@ -58,6 +52,23 @@ int check_device(const std::string& who, const fitoct_summary_config* cfg, const
 
 // (where a plan's or a batch's last run left its draws: Where, plan_where, batch_where of
 // plan_internal.h, defined in posterior_common.hip)
+
+// The last run of a plan or a batch as the arguments of a *_device_checked entry: the NULL check
+// (`who` names the table in its message; `rest`: the call's other required pointers are there),
+// the refusals of plan_where / batch_where (`needs`), and the caller's config with the device
+// of the draws in it.  f(where, config) makes the call; a plan is a run of one group.
+inline int where_of(fitoct_plan* pl, const char* needs, Where& w) { return plan_where(pl, needs, w); }
+inline int where_of(fitoct_batch* b, const char* needs, Where& w) { return batch_where(b, needs, w); }
+template <class Handle, class Config, class F>
+int on_last_run(Handle* h, const char* who, const char* needs, const Config* cfg, bool rest,
+                F&& f) {
+  if (!h || !cfg || !rest) return fail(FITOCT_E_ARG, std::string(who) + ": NULL argument");
+  Where w;
+  FITOCT_TRY(where_of(h, needs, w));
+  Config c = *cfg;
+  c.device = w.device;
+  return f(w, c);
+}
 
 // ---- what the kernels share -----------------------------------------------------------------
 // output column j of a raw row (7 sampler columns, then the parameter columns)
@@ -114,31 +125,7 @@ __device__ inline RowBlock load_row_tile(const KShape& k, const double* draws, d
   return load_row_tile(k, draws, tile, (int64_t)blockIdx.x);
 }
 
-// ---- device buffers -------------------------------------------------------------------------
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    HIP_TRY(hipMalloc(&p, bytes ? bytes : 8));
-    return FITOCT_OK;
-  }
-  template <class T>
-  T* as() const {
-    return (T*)p;
-  }
-};
-// the calling thread's device is put back when the call returns
-struct DeviceKeep {
-  int dev = -1;
-  DeviceKeep() {
-    if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-  }
-  ~DeviceKeep() {
-    if (dev >= 0) (void)hipSetDevice(dev);
-  }
-};
+// (device buffers: DevBuf; the caller's device put back: DeviceKeep -- plan_internal.h)
 
 // Items (output columns, curve pairs) per pass: as many of `items` as the staging cap holds at
 // bytes_per_item each (never less than one); the passes are i0 = 0, per, ... with

@@ -158,6 +158,18 @@ int summary_device_checked(const fitoct_problem* probs, int n_groups, int chains
 
 using namespace fitoct;
 
+// the last run of a plan or of a batch (one body: on_last_run)
+template <class Handle>
+static int32_t last_run_summary(const char* fn, Handle* h, const fitoct_summary_config* cfg, double* out) {
+  return guarded(fn, [&]() -> int32_t {
+    return on_last_run(h, "summary", "the summary needs", cfg, out != nullptr,
+                       [&](const Where& w, const fitoct_summary_config& c) {
+                         return summary_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains,
+                                                       w.iters_saved, w.draws, &c, nullptr, out);
+                       });
+  });
+}
+
 extern "C" {
 
 void fitoct_default_summary_config(fitoct_summary_config* cfg) {
@@ -192,27 +204,11 @@ int32_t fitoct_summary_device(const fitoct_problem* probs, int32_t n_groups, int
 }
 
 int32_t fitoct_plan_summary(fitoct_plan* pl, const fitoct_summary_config* cfg, double* out) {
-  return guarded(__func__, [&]() -> int32_t {
-    if (!pl || !cfg || !out) return fail(FITOCT_E_ARG, "summary: NULL argument");
-    Where w;
-    FITOCT_TRY(plan_where(pl, "the summary needs", w));
-    fitoct_summary_config c = *cfg;
-    c.device = w.device;
-    return summary_device_checked(w.probs.data(), 1, w.chains, w.iters_saved, w.draws, &c, nullptr,
-                                  out);
-  });
+  return last_run_summary(__func__, pl, cfg, out);
 }
 
 int32_t fitoct_batch_summary(fitoct_batch* b, const fitoct_summary_config* cfg, double* out) {
-  return guarded(__func__, [&]() -> int32_t {
-    if (!b || !cfg || !out) return fail(FITOCT_E_ARG, "summary: NULL argument");
-    Where w;
-    FITOCT_TRY(batch_where(b, "the summary needs", w));
-    fitoct_summary_config c = *cfg;
-    c.device = w.device;
-    return summary_device_checked(w.probs.data(), (int32_t)w.probs.size(), w.chains, w.iters_saved,
-                                  w.draws, &c, nullptr, out);
-  });
+  return last_run_summary(__func__, b, cfg, out);
 }
 
 }  // extern "C"

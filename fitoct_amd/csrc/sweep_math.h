@@ -131,7 +131,7 @@ __device__ __forceinline__ double exp11_(double x) {
 
 // Likelihood terms of one bin given its modulation dL (shared by every mode).
 // acc: [0] sum d^2, [1] sum a, [2] sum a e, [3] sum w; returns h (adjoint seed of dL).
-// yi = y / uy is staged per bin (fitoct_api.cpp stage), so d = (y - m) / uy is one FMA,
+// yi = y / uy is staged per bin (plan_data.cpp stage), so d = (y - m) / uy is one FMA,
 // and c x / L is formed once for the exponent and the theta3 weight.
 // The non-physical guard (1 + dL <= 0 -> lp = -inf) is a per-lane running min
 // (umin), applied once after the lane's bins (no per-bin selects).
